@@ -29,11 +29,22 @@ per GPU, BEFORE anything touches a GPU (it never re-executes a process that has)
 with the worst child status; it refuses to run when fewer than N devices are visible.
 
 Prints ONE JSON line on rank 0's stdout (see the driver contract; library chatter goes to stderr); `roofline`
-prices the dominant (main) kernel by HIP events on its stream, `cpu_baseline` times the CPU oracle.  The line
-carries its own footnotes, measured after the timed region (they never enter `value`): the classic schedule's
-rate, one dataset end to end without cross-dataset overlap, the cost of a wrong guess, a complex128 sub-record,
-BASELINE configs[1] and configs[4] end to end (`configs`), the README quick start against the oracle (`parity`);
-with --gpus N: `per_rank` (every rank's device period, search latency, searches owned).
+prices the dominant (main) kernel by HIP events on its stream, taken from the timed steps themselves.  With --gpus N
+the line also carries `per_rank` (every rank's device period, search latency, searches owned).
+
+A plain run sets up, warms up, times the --steps steps and prints the line, nothing more.  `--full` adds what takes
+runs of its own, measured after the timed region (it never enters `value`): `cpu_baseline` (the CPU oracle, one core
+and all cores), the classic schedule's rate, one dataset end to end without cross-dataset overlap, the cost of a
+wrong guess, the heterogeneous family's hit rate, a complex128 sub-record, BASELINE configs[1] and configs[4] end to
+end (`configs`) and the README quick start against the oracle (`parity`).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller as .npy files
+(rank 0; float32 for complex64 storage, float64 for complex128; complex values as a trailing (re, im) axis):
+    spectra_sample.npy       [R, N, 2] the spectra of R rows drawn once by a fixed seed (at most 32 MB)
+    spectra_sample_rows.npy  [R] those rows' indices
+    spectrum_winner.npy      [N, 2] the spectrum of the row that holds the global arg-max
+    autophase.npy            [6] float64: p0, p1, pivot, flat_index, target_idx, max_abs
+The inputs depend on the arguments alone (seeded generators), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -178,7 +189,13 @@ def main():
     ap.add_argument("--target-points", type=int, default=8192)
     ap.add_argument("--lb", type=float, default=5.0)
     ap.add_argument("--dtype", choices=["c64", "c128"], default="c64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the CPU baselines, the footnotes, the `configs` record and "
+                         "the parity check (each can be left out again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (a fixed sample of its spectra, the winner's spectrum, "
+                         "(p0, p1) and the arg-max) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the parity check")
     ap.add_argument("--no-overlap", action="store_true",
                     help="do not queue the next step's pre-pass while the host solves the current one")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -198,18 +215,23 @@ def main():
                     help="distinct synthetic datasets the steps rotate through (different noise, different brightest voxel)")
     ap.add_argument("--hetero-sets", type=int, default=64,
                     help="footnote: datasets of the heterogeneous family (synth_hetero) the hit rate is measured on")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` record (BASELINE configs[1] and [4] end to end)")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full: skip the `configs` record (BASELINE configs[1] and [4] end to end)")
     ap.add_argument("--only-configs", action="store_true", help="print the `configs` record alone (experiments)")
     ap.add_argument("--no-footnotes", action="store_true",
-                    help="skip the extra measurements after the timed region (classic schedule, single dataset, forced "
-                         "miss, complex128)")
+                    help="--full: skip the extra measurements after the timed region (classic schedule, single dataset, "
+                         "forced miss, complex128, configs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args, sys.argv[1:]))
 
     # the all-cores CPU baseline's worker processes are forked NOW, before anything can have touched a GPU
     cpu_pool = None
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_cpu_baseline:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_cpu_baseline:
         try:
             dt0 = 1.0 / 5000.0
             cpu_pool = CpuPool(min(16384, args.voxels), args.n_time, np.arange(args.n_time) * dt0, args.target_points, args.lb)
@@ -599,19 +621,22 @@ def main():
               f"team budget {aps.stream_threads()} threads on {len(os.sched_getaffinity(0))} CPUs, this process used "
               f"{cpu_cores:.2f} cores, ms/step {ms_per_step:.3f}",
               file=sys.stderr)
-    if not args.no_footnotes and world == 1:
+    if args.dump_outputs and rank == 0:  # before the footnotes reuse the output buffers
+        dump_outputs(torch, args.dump_outputs, out if (args.steps - 1) % 2 == 0 else out_b, timed_results[-1],
+                     rank * nv)
+    if args.full and not args.no_footnotes and world == 1:
         result.update(footnotes(torch, pipeline, dev, xs, t, (out, out_b), plan, N, args, speculate, main_ms, alg_bytes))
         if speculate and "heterogeneous" in result:
             result["speculation"]["hit_rate_heterogeneous"] = result["heterogeneous"]["hit_rate"]
         if speculate and "speculation_miss" in result:  # the hit counts above are the timed region's; this is the price
             result["speculation"]["miss_penalty_ms"] = result["speculation_miss"]["miss_penalty_ms"]
 
-    if not args.no_footnotes and not args.no_configs and world == 1:
+    if args.full and not args.no_footnotes and not args.no_configs and world == 1:
         try:
             result["configs"] = configs_note(torch, pipeline, device, args)
         except Exception as e:  # noqa: BLE001 -- a footnote must not cost the headline
             result["configs"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(x, t, N, args.lb, args.cpu_seconds, nv)
         try:  # (same leg: the oracle as the checker)
             result["parity"] = parity_note(torch, pipeline, dev, device)
@@ -629,6 +654,25 @@ def main():
         os.write(result_fd, (json.dumps(result) + "\n").encode())
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(torch, path, spectra, res, row_offset, budget_bytes=32 << 20, seed=20240611):
+    """--dump-outputs: what the last timed step handed its caller -- `spectra` (this rank's [n_rows, N] output
+    buffer) and `res` (its AutophaseResult) -- as float .npy files under `path` (names in the module docstring).
+    The spectra are sampled: rows drawn once by `seed`, as many as fit in `budget_bytes`."""
+    os.makedirs(path, exist_ok=True)
+    n_rows, N = spectra.shape
+    rd = np.float32 if spectra.dtype == torch.complex64 else np.float64
+    n_pick = max(1, min(n_rows, budget_bytes // (N * 2 * np.dtype(rd).itemsize)))
+    rows = np.sort(np.random.default_rng(seed).choice(n_rows, n_pick, replace=False))
+    picked = spectra.index_select(0, torch.from_numpy(rows).to(spectra.device))
+    np.save(os.path.join(path, "spectra_sample.npy"), torch.view_as_real(picked).cpu().numpy().astype(rd, copy=False))
+    np.save(os.path.join(path, "spectra_sample_rows.npy"), rows.astype(np.float64))
+    win = res.flat_index // N - row_offset
+    if 0 <= win < n_rows:  # (several ranks: only the rank that owns the winning row has its spectrum)
+        np.save(os.path.join(path, "spectrum_winner.npy"), torch.view_as_real(spectra[win]).cpu().numpy().astype(rd, copy=False))
+    np.save(os.path.join(path, "autophase.npy"), np.array([res.p0, res.p1, res.pivot, res.flat_index, res.target_idx,
+                                                           res.max_abs], dtype=np.float64))
 
 
 def footnotes(torch, pipeline, dev, xs, t, outs, plan, N, args, speculate, main_ms, alg_bytes):

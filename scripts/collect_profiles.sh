@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): bash scripts/collect_profiles.sh <round-tag> [part ...]
 # Regenerates the source data of profiles/<round-tag>/ (written to gpurun_out/<round-tag>/); parts (default: all):
-#   bench     bench.py unprofiled: default K/W and the driver's --steps 20 --warmup 5 -> bench_default.json, bench_steps20.json
+#   bench     bench.py --full unprofiled: default K/W and --steps 20 --warmup 5 -> bench_default.json, bench_steps20.json
 #   stats     bench.py under rocprofv3 --kernel-trace --stats -> bench_under_rocprof.json, bench_kernel_stats.csv,
 #             bench_kernel_trace_xm_kernels.csv, timeline.txt; the same for --dtype c128 -> *_c128.*
 #   pmc       separate --pmc passes (one rocprofv3 run per counter group, each with --kernel-trace only -- never with the
@@ -22,8 +22,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 has() { [[ " $parts " == *" $1 "* ]]; }
 if has bench; then
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
-  python3 bench.py --steps 20 --warmup 5 > $out/bench_steps20.json 2> $out/bench_steps20.err
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --steps 20 --warmup 5 --full > $out/bench_steps20.json 2> $out/bench_steps20.err
   python3 bench.py --dtype c128 --steps 40 --warmup 5 --no-cpu-baseline --no-footnotes > $out/bench_c128.json 2> $out/bench_c128.err
   echo "bench done"
 fi

@@ -851,3 +851,37 @@ def test_solver_team_budget(monkeypatch):
     assert aps.default_threads() == 1  # (never zero)
     monkeypatch.setenv("XM_SOLVER_THREADS", "5")
     assert aps.default_threads() == aps.burst_threads() == 5
+
+
+def test_bench_dump_outputs_and_arguments_without_gpu(tmp_path):
+    """bench.dump_outputs on host tensors: a fixed row sample within its byte budget, float arrays only, the winner's
+    row where the global flat index puts it; and bench.py refuses a step count below one before it touches a GPU."""
+    import subprocess
+    import sys
+    from types import SimpleNamespace
+
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(3)
+    for cdt, rd in ((torch.complex64, np.float32), (torch.complex128, np.float64)):
+        spec = torch.from_numpy((rng.standard_normal((300, 64)) + 1j * rng.standard_normal((300, 64))).astype(np.complex128)).to(cdt)
+        res = SimpleNamespace(p0=12.5, p1=-3.25, pivot=0.5, flat_index=1000 * 64 + 17, target_idx=17, max_abs=2.0)
+        d = tmp_path / str(rd.__name__)
+        bench.dump_outputs(torch, str(d), spec, res, row_offset=800, budget_bytes=100 * 64 * 2 * np.dtype(rd).itemsize)
+        sample, rows = np.load(d / "spectra_sample.npy"), np.load(d / "spectra_sample_rows.npy")
+        assert sample.dtype == rd and sample.shape == (100, 64, 2) and rows.dtype == np.float64
+        assert np.all(np.diff(rows) > 0) and rows.min() >= 0 and rows.max() < 300
+        assert np.array_equal(sample, torch.view_as_real(spec).numpy()[rows.astype(int)])
+        assert np.array_equal(np.load(d / "spectrum_winner.npy"), torch.view_as_real(spec[200]).numpy())
+        assert np.array_equal(np.load(d / "autophase.npy"), [12.5, -3.25, 0.5, 1000 * 64 + 17, 17, 2.0])
+        bench.dump_outputs(torch, str(d / "again"), spec, res, row_offset=800, budget_bytes=100 * 64 * 2 * np.dtype(rd).itemsize)
+        assert np.array_equal(np.load(d / "again" / "spectra_sample_rows.npy"), rows)
+        bench.dump_outputs(torch, str(d / "other_rank"), spec, res, row_offset=0)  # the winning row lives elsewhere
+        assert not (d / "other_rank" / "spectrum_winner.npy").exists()
+        assert np.load(d / "other_rank" / "spectra_sample.npy").shape == (300, 64, 2)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -388,6 +388,50 @@ def test_bench_self_launches_two_ranks():
         assert r.returncode != 0 and "device(s) visible" in r.stderr
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run measures the headline alone (no `--full` record in its line), reports the steps it was
+    given, and `--dump-outputs` writes the last timed step's outputs: float arrays within 64 MB, the winner's spectrum
+    peaking where the arg-max says, and the same arrays from a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--voxels", "4096", "--prime-ms", "0", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["dtype"] == "f32"
+        for key in ("cpu_baseline", "cpu_baseline_all_cores", "parity", "configs", "c128", "heterogeneous",
+                    "speculation_miss", "value_classic_schedule"):
+            assert key not in rec, key
+        names = sorted(os.listdir(d))
+        assert names == ["autophase.npy", "spectra_sample.npy", "spectra_sample_rows.npy", "spectrum_winner.npy"]
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        arrs = {n[:-4]: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["spectra_sample"].shape == (arrs["spectra_sample_rows"].size, 8192, 2)
+        p0, p1, pivot, flat, target_idx, max_abs = arrs["autophase"]
+        win = arrs["spectrum_winner"][..., 0] + 1j * arrs["spectrum_winner"][..., 1]
+        assert abs(abs(win[int(flat) % 8192]) - max_abs) <= 1e-5 * max_abs
+        assert np.abs(win).max() <= max_abs * (1 + 1e-5)
+        dumps.append(arrs)
+    for n, a in dumps[0].items():
+        b = dumps[1][n]
+        if n == "autophase" or n == "spectra_sample_rows":
+            assert np.array_equal(a, b), n
+        else:
+            assert float(np.abs(a - b).max()) <= 2.5e-7 * float(np.abs(a).max()), n
+
+
 def test_speculative_schedule_two_ranks_with_cross_rank_repair():
     """Two ranks (sharing this GPU, gloo + the shared-memory exchange) run run_stream(speculate=True) on shards of
     datasets whose L1-norm winner lives on rank 0 while the true maximum lives on rank 1: the verification
