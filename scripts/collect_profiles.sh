@@ -69,8 +69,6 @@ if has labs; then
   python3 tests/tool_c1_tolerance.py > $out/c1_tolerance.txt 2>/dev/null
   python3 scripts/check_device_search.py > $out/device_search.txt 2>/dev/null || true   # (two degenerate slices diverge: exit 1)
   python3 scripts/time_zf_apod.py > $out/zf_apod.txt 2>/dev/null
-  bash scripts/ab_search_engines.sh > $out/search_engines.txt 2>/dev/null; rm -f gpurun_out/ab_*.json gpurun_out/ab.err
-  bash scripts/sweep_search_workers.sh > $out/search_workers.txt 2>/dev/null; rm -f gpurun_out/sw_*.json gpurun_out/sw.err
   python3 bench.py --only-configs --no-cpu-baseline > $out/configs.json 2>/dev/null
   python3 scripts/time_configs.py > $out/time_configs.txt 2>/dev/null || true
   python3 scripts/time_fft_sweep.py > $out/fft_sweep.txt 2>/dev/null || true

@@ -21,6 +21,5 @@ fi
 run default XM_NOP=1
 run polish_threads XM_POLISH_THREADS=1
 run polish_native XMRIS_AMD_POLISH=native
-run python_threads XM_SEARCH_PYTHON_THREADS=1
 run no_hedge XMRIS_AMD_HEDGE=0
 run device_engine XMRIS_AMD_SEARCH=device

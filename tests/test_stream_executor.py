@@ -146,6 +146,8 @@ def _rank_main(rank, world, port, engine, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_WORLD_SIZE=str(world), XM_SOLVER_THREADS="1", XMRIS_AMD_SEARCH=engine,
                       XM_POLISH_THREADS="1")  # (polish helpers on a thread: eight ranks x four worker processes is a crowd)
+    if engine == "mixed":  # the ranks disagree on the engine: every rank must follow rank 0's choice
+        os.environ["XMRIS_AMD_SEARCH"] = "device" if rank == 0 else "host"
     if engine == "host":
         os.environ["XM_HEDGE_SPACING"] = "1"  # (a rank owns every seventh dataset here: the one-in-eight rule would never let it hedge twice)
         os.environ["XM_TEST_SLOW_SEARCH"] = "7,4000"  # dataset 7's search reaches its owner's search service 4 s late: started a second time
@@ -163,7 +165,7 @@ def _rank_main(rank, world, port, engine, q):
     torch.set_num_threads(1)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        shm = sharding.ShmExchange.create(dist)
+        shm = sharding.ShmExchange.create(dist, timeout_s=30.0 if engine == "mixed" else 120.0)
 
         def exchange(amax, gflat):
             owner, g, _ = shm.exchange_argmax(amax, gflat)
@@ -182,7 +184,7 @@ def _rank_main(rank, world, port, engine, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("engine", ["device", "host"])
+@pytest.mark.parametrize("engine", ["device", "host", "mixed"])
 def test_world_8_speculative_executor(monkeypatch, engine):
     """EIGHT ranks (spawned processes, gloo + the shared-memory exchange), 14 datasets, `overlap` on: the winners rotate
     over ranks 1..7 (rank 0 never owns one), two datasets are guessed wrong with the guessed row and the true row on
@@ -223,7 +225,7 @@ def test_world_8_speculative_executor(monkeypatch, engine):
             assert spec == ("repaired" if d in MISSES else "hit"), (rank, d, spec)
             assert digests[d] == hashlib.sha256(np.ascontiguousarray(ref_out[d][lo:hi].numpy()).tobytes()).hexdigest(), (rank, d)
             hedged += int(bool(hg))
-        if engine == "device":  # behind the fill (the first datasets of a call), every search a rank owns is a search kernel
+        if engine in ("device", "mixed"):  # behind the fill (the first datasets of a call), every search a rank owns is a search kernel
             # (of the GUESSED winner: a missed dataset's kernel ran on the coarse winner's rank, its repair on the host)
             owned = [d for d in range(N_SETS) if (MISSES[d][1] if d in MISSES else owners[d]) == rank]
             assert len([d for d in owned if d >= 5]) <= counts["search_launch"] <= len(owned), (rank, counts, owned)
