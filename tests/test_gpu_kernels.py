@@ -499,7 +499,7 @@ def test_guess_rows_and_refine(dev, nb, n_in, n_out, dtype):
     ref_est = (np.abs(np.fft.fft(xc, n=1024, axis=1)) ** 2).max(axis=1) / n_out
     # rows of 512 samples and more take the matrix-core kernel (csrc/xm_coarse.h: fp16 operands behind a power-of-two
     # row scale, fp32 sums): an ESTIMATE, good to 2e-3; the FFT kernel (shorter rows) to 2e-5
-    mfma = n_in >= 512 and not os.environ.get("XM_GUESS_FFT")
+    mfma = n_in >= 512
     np.testing.assert_allclose(est.cpu().numpy(), ref_est, rtol=2e-3 if mfma else 2e-5)
     assert dev.last_kernel().startswith("k_coarse_mfma" if mfma else "k_zf2p")
     full = np.abs(np.fft.fft(x.astype(np.complex128) * w[:n_in], n=n_out, axis=1)) ** 2 / n_out
@@ -532,8 +532,6 @@ def test_coarse_spectra_on_the_matrix_cores_scale_every_row(dev, dtype):
     follows; this is its ranking statistic), zero as zero, NaN as NaN, and the launch's key must name the NaN row."""
     import torch
 
-    if os.environ.get("XM_GUESS_FFT"):
-        pytest.skip("XM_GUESS_FFT: the matrix-core kernel is switched off")
     rng = np.random.default_rng(5)
     nb, n_in, n_out = 523, 1024, 2048
     t = np.arange(n_in) * 2e-4
@@ -867,6 +865,79 @@ def test_randomised_geometries_of_the_fused_entry_point(dev, oracle):
                 assert np.all(mag[np.arange(nb), idx] >= mag.max(axis=1) * (1 - 30 * tol)), tag
 
 
+# The dispatcher's routing table: for every geometry, row layout, row count and output request, the kernel the fused
+# entry point launches (`last_kernel`: family, plan, MODE, OPT) and the answers of `ramp_native` / `key_native`.
+ROUTE_GEOMETRIES = (
+    [(h, 2 * h) for h in (512, 1024, 2048, 4096, 8192)] + [(1000, 4096)]  # >= 2x zero fill
+    + [(n, n) for n in (512, 1024, 2048, 4096, 8192, 768, 1280, 1536, 3072, 5120, 6144, 16384)]
+    + [(1972, 1972), (32768, 32768)])  # chirp-z inside the LDS, four-step over global memory
+ROUTE_MODES = ("write", "phase", "ramp", "amax", "amax_only", "value_only", "phase_amax_only", "phase_value_only",
+               "ramp_value_only", "key", "key_write",
+               "key_only")
+ROUTE_GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "dispatch_routes.json")
+
+
+def _route_table(dev):
+    import torch
+
+    key, rec = dev.new_argmax_key("cuda"), dev.new_key_result()
+    table = {}
+    for dtype in ("complex64", "complex128"):
+        tdt = getattr(torch, dtype)
+        sentinel = torch.zeros((1, 512), dtype=tdt, device="cuda")
+        for n_in0, n_out in ROUTE_GEOMETRIES:
+            many = 20000 if n_out <= 1024 else 9000 if n_out <= 2048 else 2500 if n_out <= 8192 else 600
+            rows = [("al", nb, n_in0, 0, 0) for nb in (1, 2, many)] + [("odd", 2, n_in0 - 1, 1, 0)]
+            if dtype == "complex64":
+                rows.append(("off8", 2, n_in0, 0, 1))  # base pointer 8 bytes past a 16-byte boundary
+            for tag, nb, n_in, pad, off in rows:
+                flat = torch.zeros(nb * n_in + off, dtype=tdt, device="cuda")
+                x = flat[off:].view(nb, n_in)
+                phase = torch.ones(n_out, dtype=tdt, device="cuda")
+                rn, kn = dev.ramp_native(x, n_out, pad), dev.key_native(x, n_out, pad)
+                row = {"ramp_native": rn, "key_native": kn}
+                for mode in ROUTE_MODES:
+                    kw = {
+                        "write": {}, "phase": dict(phase_table=phase), "ramp": dict(phase_ramp=(0.1, 0.01)),
+                        "amax": dict(want_argmax=True), "amax_only": dict(want_out=False, want_argmax=True),
+                        "value_only": dict(want_out=False, want_argmax=True, argmax_value_only=True),
+                        "phase_amax_only": dict(phase_table=phase, want_out=False, want_argmax=True),
+                        "phase_value_only": dict(phase_table=phase, want_out=False, want_argmax=True,
+                                                 argmax_value_only=True),
+                        "ramp_value_only": dict(phase_ramp=(0.1, 0.01), want_argmax=True, argmax_value_only=True),
+                        "key": dict(phase_ramp=(0.1, 0.01), global_key=key, key_result=rec),
+                        "key_write": dict(global_key=key, key_result=rec),
+                        "key_only": dict(want_out=False, global_key=key, key_result=rec),
+                    }[mode]
+                    if mode.startswith("key") and not (kn and (mode == "key" or dtype == "complex128")):
+                        continue  # (complex64 keys are taken in the ramp form only)
+                    dev.pipeline_fused(sentinel, 512)  # a launch that notes itself: a path that notes nothing shows it
+                    try:
+                        dev.pipeline_fused(x, n_out, pad, **kw)
+                        row[mode] = dev.last_kernel()
+                    except Exception:
+                        row[mode] = "refused"
+                torch.cuda.synchronize()
+                table[f"{dtype} {n_in}+{pad}>{n_out} {tag} nb={nb}"] = row
+    return table
+
+
+def test_dispatch_routes_match_the_recorded_table(dev):
+    """The fused entry point's routing decision, pinned: every case of `_route_table` launches the kernel (template,
+    plan, MODE and OPT words) recorded in tests/golden/dispatch_routes.json, and `ramp_native` / `key_native` give the
+    recorded answers -- covering both precisions, the >= 2x zero fill at every half length, the plain transforms
+    (with the 1536-point special case), 16384, chirp-z and four-step lengths, aligned / odd / 8-byte-offset rows,
+    one, two and many rows, and every output request."""
+    import json
+
+    with open(ROUTE_GOLDEN) as f:
+        want = json.load(f)
+    got = _route_table(dev)
+    assert sorted(got) == sorted(want)
+    diff = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not diff, diff
+
+
 @pytest.mark.parametrize("case", [
     # (n_batch, n_in, n_out, pad_left, in dtype, promote)
     (9, 1024, 2048, 0, "complex64", False), (9, 1024, 2048, 0, "complex64", True), (9, 1024, 2048, 0, "complex128", False),
@@ -898,3 +969,29 @@ def test_zero_fill_apodize_one_launch(dev, case):
     # a second launch on the same queue slot ring (the last workgroup out must have left the counters zero)
     again = dev.zf_apod(dev.to_device(x), n_out, pad_left, w, promote=promote).cpu().numpy()
     assert np.array_equal(again.view(np.uint8), ref.view(np.uint8))
+
+
+def test_zero_fill_apodize_occupancy_follows_the_window_size():
+    """`xm_zf_apod`'s dynamic LDS is the window over the acquired samples, so it changes from call to call: through the
+    same kernel (complex64 rows promoted to complex128), a small window first (2048 samples, 16 KiB), then 12288 samples
+    (96 KiB) -- the second launch needs its own occupancy and LDS opt-in.  In a fresh process, so that nothing before
+    it has set up either size."""
+    import subprocess
+    import sys
+
+    code = """
+import numpy as np, torch
+from xmris_amd import device as dev
+rng = np.random.default_rng(3)
+for nb, n_in in ((7, 2048), (5, 12288)):  # (zf_apod_supported: 12288 complex128 points are the largest window)
+    x = (rng.standard_normal((nb, n_in)) + 1j * rng.standard_normal((nb, n_in))).astype(np.complex64)
+    w = np.exp(-np.arange(12288) / 3000.0)
+    got = dev.zf_apod(dev.to_device(x), 12288, 0, w, promote=True).cpu().numpy()
+    ref = np.zeros((nb, 12288), dtype=np.complex128)
+    ref[:, :n_in] = x.astype(np.complex128) * w[:n_in][None, :]
+    assert np.array_equal(got.view(np.uint8), ref.view(np.uint8)), n_in
+print("ok")
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr

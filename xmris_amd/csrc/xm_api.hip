@@ -76,8 +76,7 @@ bool xm_has_direct_plan(int n, int dtype) {
 int xm_bluestein_m(int n) {  // smallest convolution length with a plan >= max(2n-1, 16): 2^k, or 3 * 2^k where built
   int m = 16;
   while (m < 2 * n - 1) m <<= 1;
-  static const bool pow2_only = getenv("XM_BLUE_POW2") != nullptr;  // tuning switch
-  if (!pow2_only && m == 4096 && 2 * n - 1 <= 3072) return 3072;
+  if (m == 4096 && 2 * n - 1 <= 3072) return 3072;
   return m;
 }
 
@@ -266,16 +265,13 @@ static int launch_zf_apod(const void* in, int64_t in_stride, void* out, const vo
   if (rc) return rc;
   int resident = 0;
   if (vec) {
-    static XmResidency res;
-    rc = xm_resident_blocks(res, k_zf_apod<TI, TO, true>, 256, lds, &resident, st);
-    if (rc) return rc;
     // Few workgroups per CU: measured on 65,536 x 4096 -> 8192 complex64 with 1 / 2 / 3 / 4 / 5 per CU: 3.27 / 5.40 /
     // 5.63 / 5.34 / 5.33 TB/s, with ten 4.73; rows of complex128 out (twice the bytes per workgroup and step): 2 / 3 / 4
     // per CU 5.48 / 5.31 / 5.06, promoted complex64 -> complex128 4.77 / 4.21 / 3.96 (profiles/r04/zf_apod.txt) -- a
     // streaming copy wants few, deep streams: three for 8-byte outputs, two for 16-byte ones
-    static const int wgs_env = getenv("XM_ZFAPOD_WGS") ? atoi(getenv("XM_ZFAPOD_WGS")) : (sizeof(TO) == 4 ? 3 : 2);  // tuning switch
-    int cus = 0;
-    if (wgs_env > 0 && xm_stream_cu_count(st, &cus) == XM_OK && cus > 0 && resident > wgs_env * cus) resident = wgs_env * cus;
+    static XmResidency res;
+    rc = xm_resident_blocks(res, k_zf_apod<TI, TO, true>, 256, lds, &resident, st, sizeof(TO) == 4 ? 3 : 2);
+    if (rc) return rc;
     const long long blocks = n_batch < resident ? n_batch : resident;
     xm_note_kernel("k_zf_apod", nullptr, sizeof(TI) == 4 ? (sizeof(TO) == 4 ? "float, float" : "float, double") : "double, double", 1, -1);
     hipLaunchKernelGGL((k_zf_apod<TI, TO, true>), dim3((unsigned)blocks), dim3(256), lds, st, A);
@@ -737,9 +733,8 @@ int xm_pipeline_ramp_native(const void* in, int64_t in_row_stride, int n_in, int
 int xm_pipeline_key_native(const void* in, int64_t in_row_stride, int n_in, int n_out, int pad_left, unsigned flags,
                            int dtype) {
   if ((dtype != XM_C64 && dtype != XM_C128) || n_in < 1 || pad_left < 0 || pad_left + n_in > n_out) return 0;
-  if (dtype == XM_C64) return xm_key_native_f32(in, in_row_stride, n_in, n_out, pad_left, flags);
-  static const bool gen1 = getenv("XM_ZF2D_GEN1") != nullptr;  // (tuning switch: k_zf2<double> has no key)
-  return !gen1 && xm_key_native_f64(in, in_row_stride, n_in, n_out, pad_left, flags);
+  return dtype == XM_C64 ? xm_key_native_f32(in, in_row_stride, n_in, n_out, pad_left, flags)
+                         : xm_key_native_f64(in, in_row_stride, n_in, n_out, pad_left, flags);
 }
 
 int xm_fft1d_batched(const void* in, void* out, int64_t n_batch, int n, unsigned flags, int dtype, void* stream) {

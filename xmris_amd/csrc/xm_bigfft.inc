@@ -142,8 +142,6 @@ bool big_split(int n, int* n1, int* n2) {
   return true;
 }
 
-int pipeline_tables(PipeArgs<T>& A, int n_out, bool zf2, hipStream_t st);
-
 // plain forward transform of `rows` contiguous rows of length m (an in-LDS plan)
 int big_rows_fft(const Cx<T>* in, Cx<T>* out, long long rows, int m, hipStream_t st) {
   PipeArgs<T> S;
@@ -154,7 +152,7 @@ int big_rows_fft(const Cx<T>* in, Cx<T>* out, long long rows, int m, hipStream_t
   S.n_batch = rows;
   S.n = S.n_in = m;
   S.scale = T(1);
-  return pipeline_tables(S, m, false, st);
+  return run(route(in, m, rows, m, m, 0, 0, W), S, m, nullptr, st);
 }
 
 // four-step transform of length n = n1 n2: P describes the input, E the output; scratch S0, S1: n_batch * n elements each

@@ -132,26 +132,19 @@ __global__ __launch_bounds__(64 * kCoarseWaves, 2) void k_coarse_mfma(CoarseArgs
     const xm_f2* __restrict__ row = reinterpret_cast<const xm_f2*>(A.in) + s * A.in_stride;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-#if !defined(XM_COARSE_NT) || XM_COARSE_NT
       const xm_f2 v = __builtin_nontemporal_load(row + 32u * (8u * h + (unsigned)j) + r);
-#else
-      const xm_f2 v = row[32u * (8u * h + (unsigned)j) + r];
-#endif
       x[j] = mk<float>(v.x, v.y);
     }
   };
 
   unsigned best_key = 0u, best_row = 0u;
   bool have = false;
-  // rows loaded ahead of the one being transformed (XM_COARSE_DEPTH, XM_COARSE_NT: compile-time A/B switches).
+  // rows loaded ahead of the one being transformed, with nontemporal loads.
   // Standalone on 65,536 rows, three rounds (profiles/r04/coarse_kernel.txt): depth 1 plain loads 56.6-57.4 us, depth 1
   // nontemporal 60.0-60.8, depth 2 plain 58.4-58.6, depth 2 nontemporal 62.2-63.7 -- a second row in flight buys
   // nothing (8 waves per CU already hold 32 KiB), and the nontemporal hint costs 4 us here but gives the kernels
   // queued behind it their tables back (in the stream: refine 36.1 -> 33.7 us, the fp64 transform 21.2 -> 17.3).
-#ifndef XM_COARSE_DEPTH
-#define XM_COARSE_DEPTH 1
-#endif
-  constexpr int DEPTH = XM_COARSE_DEPTH;
+  constexpr int DEPTH = 1;
   Cx<float> nx[DEPTH][8];
   long long s = wave;
 #pragma unroll

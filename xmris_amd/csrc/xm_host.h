@@ -4,8 +4,12 @@
 #include "../../include/xmris_hip.h"
 #include "xm_common.h"
 
+#include <cmath>
+#include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <typeinfo>
 #include <vector>
 
@@ -55,6 +59,12 @@ int xm_key_native_f32(const void* in, int64_t in_stride, int n_in, int n_out, in
 int xm_key_native_f64(const void* in, int64_t in_stride, int n_in, int n_out, int pad_left, unsigned flags);
 
 // xm_launch_zf2p.hip: guess stage of the speculative schedule (xm_guess_* in xmris_hip.h)
+template <class T>
+struct PipeArgs;  // xm_kernels.h
+// xm_launch_zf2p.hip / xm_launch_zf2d.hip: the packed complex64 and the complex128 ">= 2x zero fill" kernels of half
+// length h, `mode` = ZF2_* words as route() (xm_launch.inc) decides them, `ramp` = {a, b} when mode has ZF2_RAMP
+int xm_zf2p_launch(int h, int mode, const PipeArgs<float>& A, const double* ramp, hipStream_t st);
+int xm_zf2d_launch(int h, int mode, const PipeArgs<double>& A, const double* ramp, hipStream_t st);
 int xm_zf2p_guess_supported(const void* in, int64_t in_stride, int n_in, int n_out, int pad_left, unsigned flags, int dtype);
 int xm_zf2p_guess_rows(const void* in, int64_t in_stride, const float* window, int64_t n_batch, int n_in, int n_out,
                        int n_guess, float scale, float* est, unsigned long long* key, int dtype, hipStream_t st);
@@ -74,38 +84,75 @@ int xm_ramp_table_async(void* table, int n, double phase0, double dphase, int dt
 // streams with a partition of the chip).  Cached per stream handle.
 extern "C" int xm_stream_cu_count(hipStream_t st, int* cus);  // (C linkage: defined among the ABI functions)
 
-// Grid of a persistent kernel = CUs of its stream x resident workgroups per CU.  The occupancy query and the
-// dynamic-LDS opt-in run once per kernel instantiation and device, under a lock (the launchers are re-entrant).
+// Grid of a persistent kernel = CUs of its stream x resident workgroups per CU, at most `max_per_cu` when that is > 0
+// (streaming kernels that want few, deep streams).  The occupancy query runs once per kernel instantiation, device and
+// dynamic LDS size, under a lock (the launchers are re-entrant); the dynamic-LDS opt-in follows the largest size asked.
 struct XmResidency {
   std::mutex mu;
-  int blocks[16] = {0};  // resident workgroups per CU
+  std::map<std::pair<int, size_t>, int> blocks;  // (device, dynamic LDS bytes) -> resident workgroups per CU
+  size_t opt_in[16] = {0};                       // dynamic LDS bytes opted in per device
 };
 template <class K>
-int xm_resident_blocks(XmResidency& r, K kern, int nt, size_t lds, int* out, hipStream_t st = nullptr) {
+int xm_resident_blocks(XmResidency& r, K kern, int nt, size_t lds, int* out, hipStream_t st = nullptr, int max_per_cu = 0) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 16) return xm_fail(XM_ERR_INVALID_ARG, "device ordinal out of range");
   int per_cu = 0;
   {
     std::lock_guard<std::mutex> lk(r.mu);
-    if (r.blocks[dev] == 0) {
-      if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024 && lds > r.opt_in[dev]) {
+      HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      r.opt_in[dev] = lds;
+    }
+    auto it = r.blocks.find({dev, lds});
+    if (it == r.blocks.end()) {
       int q = 0;
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kern, nt, lds));
-      r.blocks[dev] = q < 1 ? 1 : q;
+      it = r.blocks.emplace(std::make_pair(dev, lds), q < 1 ? 1 : q).first;
     }
-    per_cu = r.blocks[dev];
+    per_cu = it->second;
   }
-  // (tuning switch XM_RESIDENT_CAP=<workgroups per CU>: an upper bound for every persistent grid -- the sweep that found
-  // k_zf_apod's three per CU, profiles/r04/zf_apod.txt, applied to the other kernels: profiles/r04/resident_cap.txt)
-  static const int cap_env = getenv("XM_RESIDENT_CAP") ? atoi(getenv("XM_RESIDENT_CAP")) : 0;
-  if (cap_env > 0 && per_cu > cap_env) per_cu = cap_env;
+  if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;
   int cus = 0;
   const int rc = xm_stream_cu_count(st, &cus);
   if (rc) return rc;
   *out = per_cu * cus;
   return XM_OK;
+}
+
+// Calls f(std::integral_constant<int, MODE>) for the one MODE of Ms equal to the runtime `mode`: Ms lists the ZF2_* mode
+// words a kernel family is built with, so a request outside them is an error, never a silent fall-back.
+template <int... Ms, class F>
+int xm_with_mode(int mode, F&& f) {
+  int rc = XM_OK;
+  const bool hit = ((mode == Ms ? (rc = f(std::integral_constant<int, Ms>{}), true) : false) || ...);
+  return hit ? rc : xm_fail(XM_ERR_INVALID_ARG, "no kernel built for mode " + std::to_string(mode));
+}
+
+// Wave-uniform factors of the kernels that apply the linear phase e^{i (a + b k)} natively: ramp_c[2q], ramp_c[2q+1] =
+// e^{i (a + b base_q)} with base_q = M NT q + (output roll) mod M N -- M = 2 for the paired half-length transforms
+// (outputs 2t and 2t + 1 of a thread; ramp_e = e^{i b} for the odd bins), M = 1 for k_fft2.  `ramp` = {a, b}.
+template <class PL, bool PAIRED, class Args>
+void xm_set_ramp(Args& A, const double* ramp) {
+  using R = typename std::remove_reference<decltype(A.ramp_c[0])>::type;
+  constexpr long long M = PAIRED ? 2 : 1;
+  for (int q = 0; q < PL::P; ++q) {
+    const long long base = (M * PL::NT * q + A.out_shift) % (M * PL::N);
+    const double a = ramp[0] + ramp[1] * (double)base;
+    A.ramp_c[2 * q] = (R)std::cos(a);
+    A.ramp_c[2 * q + 1] = (R)std::sin(a);
+  }
+  if (PAIRED) {
+    A.ramp_e[0] = (R)std::cos(ramp[1]);
+    A.ramp_e[1] = (R)std::sin(ramp[1]);
+  }
+  A.ramp_db = ramp[1];
+  A.phase = nullptr;
+}
+
+// complex64 pair loads: every (even, odd) sample pair of a row is one aligned 16-byte word
+inline bool xm_pair_loads_ok(const void* in, int64_t in_stride, int n_in, int pad_left) {
+  return (pad_left % 2 == 0) && (n_in % 2 == 0) && (in_stride % 2 == 0) && ((reinterpret_cast<size_t>(in) & 15u) == 0);
 }
 
 // What the dispatcher launched last on this thread, as the profiler names it (`xm_last_kernel_string`): the fused

@@ -9,32 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 
-// xm_launch_zf2p.hip
-bool xm_zf2p_eligible(const PipeArgs<float>& A, int64_t in_stride);
-int xm_zf2p_launch(int h, const PipeArgs<float>& A, const double* ramp, hipStream_t st);
-
-// xm_launch_zf2d.hip: complex128, half lengths 4096 and 8192.  *handled = false: not one of its modes
-int xm_zf2d_launch(int h, const PipeArgs<double>& A, const double* ramp, hipStream_t st, bool* handled);
-
 namespace {
-
-inline int zf2d_launch(int h, const PipeArgs<double>& A, const double* ramp, hipStream_t st, bool* handled) {
-  return xm_zf2d_launch(h, A, ramp, st, handled);
-}
-inline int zf2d_launch(int, const PipeArgs<float>&, const double*, hipStream_t, bool* handled) {
-  *handled = false;
-  return XM_OK;
-}
-
-// complex64 reaches the second-generation hot kernel; complex128 has none
-inline bool hot_eligible(const PipeArgs<float>& A, int64_t in_stride) { return xm_zf2p_eligible(A, in_stride); }
-inline bool hot_eligible(const PipeArgs<double>&, int64_t) { return false; }
-inline int hot_launch(int h, const PipeArgs<float>& A, const double* ramp, hipStream_t st) {
-  return xm_zf2p_launch(h, A, ramp, st);
-}
-inline int hot_launch(int, const PipeArgs<double>&, const double*, hipStream_t) {
-  return xm_fail(XM_ERR_INVALID_ARG, "no packed kernel for complex128");
-}
 
 using T = XM_REAL;
 constexpr int kDtype = sizeof(T) == 8 ? XM_C128 : XM_C64;
@@ -200,17 +175,14 @@ int launch_zf2_mode(PipeArgs<T> A, hipStream_t st) {
   long long blocks = A.n_batch < resident ? A.n_batch : resident;
   if constexpr (sizeof(T) == 8 && (MODE & ZF2_WRITE) != 0) {
     // complex128 write modes are HBM bound: rows handed out dynamically, ~96 KiB of traffic per ticket (xm_zf2p.h)
-    static const bool no_queue = getenv("XM_ZF2D_NOQUEUE") != nullptr;  // tuning switch
-    if (!no_queue) {
-      const long long row_bytes = (long long)sizeof(Cx<T>) * ((long long)A.n_in + 2 * PL::N);
-      long long chunk = (98304 + row_bytes - 1) / row_bytes;
-      chunk = chunk < 1 ? 1 : (chunk > 64 ? 64 : chunk);
-      A.queue_chunk = (int)chunk;
-      const long long nchunks = (A.n_batch + chunk - 1) / chunk;
-      blocks = nchunks < resident ? nchunks : resident;
-      rc = xm_queue_slot(&A.queue);
-      if (rc) return rc;
-    }
+    const long long row_bytes = (long long)sizeof(Cx<T>) * ((long long)A.n_in + 2 * PL::N);
+    long long chunk = (98304 + row_bytes - 1) / row_bytes;
+    chunk = chunk < 1 ? 1 : (chunk > 64 ? 64 : chunk);
+    A.queue_chunk = (int)chunk;
+    const long long nchunks = (A.n_batch + chunk - 1) / chunk;
+    blocks = nchunks < resident ? nchunks : resident;
+    rc = xm_queue_slot(&A.queue);
+    if (rc) return rc;
   }
   if constexpr (sizeof(T) == 4 && (MODE & ZF2_AMAX) != 0 && (PL::NT > XM_WAVE)) {
     // value-only maxima are accumulated with one atomic max per wave: the slots start at +0.0
@@ -220,38 +192,6 @@ int launch_zf2_mode(PipeArgs<T> A, hipStream_t st) {
   hipLaunchKernelGGL((k_zf2<T, PL, MODE>), dim3((unsigned)blocks), dim3(PL::NT), lds, st, A);
   HIP_TRY(hipGetLastError());
   return XM_OK;
-}
-
-template <class PL>
-int launch_zf2(PipeArgs<T> A, hipStream_t st, const double* ramp = nullptr) {
-  const bool wr = A.out != nullptr, ph = A.phase != nullptr, am = A.absmax2 != nullptr;
-  if constexpr (sizeof(T) == 8) {
-    if (ramp && wr) {  // linear phase in closed form (factorisation: xm_zf2p.h), complex128
-      constexpr unsigned N = 2 * PL::N;
-      for (int q = 0; q < PL::P; ++q) {
-        const unsigned base = (2u * PL::NT * q + (unsigned)A.out_shift) & (N - 1u);
-        const double a = ramp[0] + ramp[1] * (double)base;
-        A.ramp_c[2 * q] = std::cos(a);
-        A.ramp_c[2 * q + 1] = std::sin(a);
-      }
-      A.ramp_e[0] = std::cos(ramp[1]);
-      A.ramp_e[1] = std::sin(ramp[1]);
-      A.ramp_db = ramp[1];
-      A.phase = nullptr;
-      if (am && A.amax_value_only) return launch_zf2_mode<PL, ZF2_WRITE | ZF2_RAMP | ZF2_AMAX | ZF2_VALUE_ONLY>(A, st);
-      if (am) return launch_zf2_mode<PL, ZF2_WRITE | ZF2_RAMP | ZF2_AMAX>(A, st);
-      return launch_zf2_mode<PL, ZF2_WRITE | ZF2_RAMP>(A, st);
-    }
-    // complex128 write + maxima: the variant compiled without the index scan
-    if (wr && am && A.amax_value_only)
-      return ph ? launch_zf2_mode<PL, ZF2_WRITE | ZF2_PHASE | ZF2_AMAX | ZF2_VALUE_ONLY>(A, st)
-                : launch_zf2_mode<PL, ZF2_WRITE | ZF2_AMAX | ZF2_VALUE_ONLY>(A, st);
-  }
-  if (wr && ph && am) return launch_zf2_mode<PL, ZF2_WRITE | ZF2_PHASE | ZF2_AMAX>(A, st);
-  if (wr && ph) return launch_zf2_mode<PL, ZF2_WRITE | ZF2_PHASE>(A, st);
-  if (wr && am) return launch_zf2_mode<PL, ZF2_WRITE | ZF2_AMAX>(A, st);
-  if (wr) return launch_zf2_mode<PL, ZF2_WRITE>(A, st);
-  return launch_zf2_mode<PL, ZF2_AMAX>(A, st);
 }
 
 // generic persistent kernel (complex64 only): two spectra per packed lane pair
@@ -286,88 +226,6 @@ int launch_fft2_mode(PipeArgs<T> A, hipStream_t st) {
   }
 }
 
-template <class PL>
-int launch_fft2(const PipeArgs<T>& A0, hipStream_t st, const double* ramp = nullptr) {
-  PipeArgs<T> A = A0;
-  const bool wr = A.out != nullptr, ph = A.phase != nullptr, am = A.absmax2 != nullptr;
-  if constexpr (sizeof(T) == 4 && PL::P <= 16) {
-    if (ramp && wr) {  // e^{i (a + b k)}, k = base_q + t: the wave-uniform factors (k_fft2, ZF2_RAMP)
-      for (int q = 0; q < PL::P; ++q) {
-        const int base = (PL::NT * q + A.out_shift) % PL::N;
-        const double a = ramp[0] + ramp[1] * (double)base;
-        A.ramp_c[2 * q] = (T)std::cos(a);
-        A.ramp_c[2 * q + 1] = (T)std::sin(a);
-      }
-      A.ramp_db = ramp[1];
-      A.phase = nullptr;
-      if (am && A.gkey) return launch_fft2_mode<PL, ZF2_WRITE | ZF2_RAMP | ZF2_AMAX | ZF2_GKEY>(A, st);
-      return am ? launch_fft2_mode<PL, ZF2_WRITE | ZF2_RAMP | ZF2_AMAX>(A, st) : launch_fft2_mode<PL, ZF2_WRITE | ZF2_RAMP>(A, st);
-    }
-  }
-  if (ramp) return xm_fail(XM_ERR_INVALID_ARG, "k_fft2: no native ramp for this plan");
-  if (wr && ph && am) return launch_fft2_mode<PL, ZF2_WRITE | ZF2_PHASE | ZF2_AMAX>(A, st);
-  if (wr && ph) return launch_fft2_mode<PL, ZF2_WRITE | ZF2_PHASE>(A, st);
-  if (wr && am) return launch_fft2_mode<PL, ZF2_WRITE | ZF2_AMAX>(A, st);
-  if (wr) return launch_fft2_mode<PL, ZF2_WRITE>(A, st);
-  return launch_fft2_mode<PL, ZF2_AMAX>(A, st);
-}
-
-#define XM_CASE_F2(N, NT, ...) \
-  case N:                      \
-    return launch_fft2<typename Zf2PlanOf<N>::type>(A, st, ramp);
-
-// threads of the k_fft2 plan of length n whose kernel applies a linear phase natively (ZF2_RAMP: at most 16 points per
-// thread), 0 when there is none
-int fft2_ramp_threads(int n) {
-  if constexpr (sizeof(T) == 4) {
-    switch (n) {
-      case 512: return 64;
-      case 1024: return 128;
-      case 2048: return 256;
-      case 4096: return 512;
-      case 8192: return 1024;
-      case 768: return 64;
-      case 1536: return 128;
-      case 3072: return 256;
-      case 6144: return 512;
-      default: break;
-    }
-  }
-  return 0;
-}
-
-// returns 1 when the length has no k_fft2 plan (the caller falls back to k_pipe)
-int dispatch_fft2(int n, const PipeArgs<T>& A, hipStream_t st, bool* handled, const double* ramp = nullptr) {
-  *handled = true;
-  if constexpr (sizeof(T) == 4) {
-    switch (n) {
-      XM_PLANS_ZF2(XM_CASE_F2)
-      XM_PLANS_FFT2_EXTRA(XM_CASE_F2)
-      case 1536:  // BASELINE configs[4]: 128 threads x 12 points x 2 spectra
-        if (!ramp && A.out && !A.absmax2)  // the plain transform (staged seam): one wave x 24 points, xm_plans.h
-          return A.phase ? launch_fft2_mode<typename Plan1536Wide::type, ZF2_WRITE | ZF2_PHASE>(A, st)
-                         : launch_fft2_mode<typename Plan1536Wide::type, ZF2_WRITE>(A, st);
-        return launch_fft2<typename PlanOf<1536>::type>(A, st, ramp);
-      case 3072:  // 3*2^k / 5*2^k: 12 or 20 points per thread, radix-4 stages (2.5x / 1.6x / 2.7x k_pipe)
-        return launch_fft2<typename PlanOf<3072>::type>(A, st, ramp);
-      case 5120:
-        return launch_fft2<typename PlanOf<5120>::type>(A, st);
-      case 768:
-        return launch_fft2<typename PlanOf<768>::type>(A, st, ramp);
-      case 1280:
-        return launch_fft2<typename PlanOf<1280>::type>(A, st);
-      case 2560:
-        return launch_fft2<typename PlanOf<2560>::type>(A, st);
-      case 6144:
-        return launch_fft2<typename PlanOf<6144>::type>(A, st, ramp);
-      default:
-        break;
-    }
-  }
-  *handled = false;
-  return XM_OK;
-}
-
 // scalar persistent kernel (used for complex128)
 template <class PL, int MODE>
 int launch_fft1_mode(PipeArgs<T> A, hipStream_t st) {
@@ -388,95 +246,6 @@ int launch_fft1_mode(PipeArgs<T> A, hipStream_t st) {
   hipLaunchKernelGGL((k_fft1<T, PL, MODE>), dim3((unsigned)blocks), dim3(PL::NT), lds, st, A);
   HIP_TRY(hipGetLastError());
   return XM_OK;
-}
-
-template <class PL>
-int launch_fft1(const PipeArgs<T>& A, hipStream_t st) {
-  const bool wr = A.out != nullptr, ph = A.phase != nullptr, am = A.absmax2 != nullptr;
-  if (wr && ph && am) return launch_fft1_mode<PL, ZF2_WRITE | ZF2_PHASE | ZF2_AMAX>(A, st);
-  if (wr && ph) return launch_fft1_mode<PL, ZF2_WRITE | ZF2_PHASE>(A, st);
-  if (wr && am) return launch_fft1_mode<PL, ZF2_WRITE | ZF2_AMAX>(A, st);
-  if (wr) return launch_fft1_mode<PL, ZF2_WRITE>(A, st);
-  return launch_fft1_mode<PL, ZF2_AMAX>(A, st);
-}
-
-int dispatch_fft1(int n, const PipeArgs<T>& A, hipStream_t st, bool* handled) {
-  *handled = true;
-  if constexpr (sizeof(T) == 8) {
-    // measured (complex128, 1 GiB of rows, read + write): 5.1-5.4 TB/s for 512...4096, 4.9 TB/s for 8192 (k_pipe:
-    // 3.1-3.6); 512 and 4096 prefer the 8-point plans, 1024 / 2048 / 8192 the 16-point ones
-    switch (n) {
-      case 1024: return launch_fft1<typename PlanOf<1024>::type>(A, st);
-      case 2048: return launch_fft1<typename PlanOf<2048>::type>(A, st);
-      case 512: return launch_fft1<typename Zf2PlanOf<512>::type>(A, st);
-      case 4096: return launch_fft1<typename Zf2PlanOf<4096>::type>(A, st);
-      case 8192: return launch_fft1<typename PlanOf<8192>::type>(A, st);
-      case 768: return launch_fft1<typename PlanOf<768>::type>(A, st);
-      case 1280: return launch_fft1<typename PlanOf<1280>::type>(A, st);
-      case 1536: return launch_fft1<typename PlanOf<1536>::type>(A, st);
-      case 2560: return launch_fft1<typename PlanOf<2560>::type>(A, st);
-      case 3072: return launch_fft1<typename PlanOf<3072>::type>(A, st);
-      case 5120:
-        return launch_fft1<typename PlanOf<5120>::type>(A, st);
-      case 6144:
-        return launch_fft1<typename PlanOf<6144>::type>(A, st);
-      default:
-        break;
-    }
-  }
-  *handled = false;
-  return XM_OK;
-}
-
-// 16384: radix 16 for complex64; complex128 exchanges plane by plane (xm_plans.h)
-// convolution length 3072 of the chirp-z kernels: the odd factor last (compute bound: with the seam's 12.4.4.4.4 the
-// kernel was 25 % SLOWER than with M = 4096)
-using PlanBlue3072 = FftPlan<3072, 256, 4, 4, 4, 4, 12>;
-// k_pipe, complex64: the plane-by-plane exchange (68 KiB) and 64 VGPRs leave room for two 1024-thread workgroups per CU,
-// one loading / storing while the other transforms: 2.7 -> 3.1 TB/s
-using Plan16kPipe = std::conditional<sizeof(T) == 4, SplitPlan<FftPlan<16384, 1024, 8, 8, 8, 8, 4>>, Plan16kD::type>::type;
-using Plan16k = std::conditional<sizeof(T) == 4, PlanOf<16384>::type, Plan16kD::type>::type;
-
-#define XM_CASE_G(N, NT, ...) \
-  case N:                     \
-    return launch_plan<typename PlanOf<N>::type, KS_GENERIC>(A, st);
-#define XM_CASE_Z(N, NT, ...) \
-  case N:                     \
-    return launch_zf2<typename Zf2PlanOf<N>::type>(A, st, ramp);
-#define XM_CASE_B(N, NT, ...) \
-  case N:                     \
-    return launch_plan<typename PlanOf<N>::type, KS_BLUESTEIN>(A, st);
-
-int dispatch_generic(int n, const PipeArgs<T>& A, hipStream_t st) {
-  switch (n) {
-    XM_PLANS_POW2(XM_CASE_G)
-    XM_PLANS_OTHER(XM_CASE_G)
-    case 16384:
-      return launch_plan<Plan16kPipe, KS_GENERIC>(A, st);
-    default:
-      break;
-  }
-  return xm_fail(XM_ERR_UNSUPPORTED_N, "no in-LDS plan for length " + std::to_string(n));
-}
-
-int dispatch_zf2(int h, const PipeArgs<T>& A, hipStream_t st, const double* ramp = nullptr) {
-  if constexpr (sizeof(T) == 4) {
-    // h = 4096 (the 4096 -> 8192 roofline shape): 256 threads x 16 points, radices 16.16.16 -- two LDS
-    // exchanges instead of three (the exchanges run at the ds_write rate), 2 workgroups/CU
-    if (h == 4096) return launch_zf2<typename PlanOf<4096>::type>(A, st);
-  } else {
-    if (h == 4096) {  // the two-workgroups-per-CU kernel takes its modes
-      bool handled = false;
-      const int rc = zf2d_launch(h, A, ramp, st, &handled);
-      if (handled) return rc;
-    }
-  }
-  switch (h) {
-    XM_PLANS_ZF2(XM_CASE_Z)
-    default:
-      break;
-  }
-  return xm_fail(XM_ERR_UNSUPPORTED_N, "no half-length plan for " + std::to_string(h));
 }
 
 // persistent Bluestein kernel: packed pairs for complex64, one spectrum per pass for complex128
@@ -504,138 +273,311 @@ int launch_blue_mode(PipeArgs<T> A, hipStream_t st) {
   return XM_OK;
 }
 
-template <class PL, bool PAIRS = (sizeof(T) == 4)>
-int launch_blue(const PipeArgs<T>& A, hipStream_t st) {
-  const bool wr = A.out != nullptr, ph = A.phase != nullptr, am = A.absmax2 != nullptr;
-  if (wr && ph && am) return launch_blue_mode<PL, ZF2_WRITE | ZF2_PHASE | ZF2_AMAX, PAIRS>(A, st);
-  if (wr && ph) return launch_blue_mode<PL, ZF2_WRITE | ZF2_PHASE, PAIRS>(A, st);
-  if (wr && am) return launch_blue_mode<PL, ZF2_WRITE | ZF2_AMAX, PAIRS>(A, st);
-  if (wr) return launch_blue_mode<PL, ZF2_WRITE, PAIRS>(A, st);
-  return launch_blue_mode<PL, ZF2_AMAX, PAIRS>(A, st);
+// 16384: radix 16 for complex64; complex128 exchanges plane by plane (xm_plans.h)
+// convolution length 3072 of the chirp-z kernels: the odd factor last (compute bound: with the seam's 12.4.4.4.4 the
+// kernel was 25 % SLOWER than with M = 4096)
+using PlanBlue3072 = FftPlan<3072, 256, 4, 4, 4, 4, 12>;
+// k_pipe, complex64: the plane-by-plane exchange (68 KiB) and 64 VGPRs leave room for two 1024-thread workgroups per CU,
+// one loading / storing while the other transforms: 2.7 -> 3.1 TB/s
+using Plan16kPipe = std::conditional<sizeof(T) == 4, SplitPlan<FftPlan<16384, 1024, 8, 8, 8, 8, 4>>, Plan16kD::type>::type;
+using Plan16k = std::conditional<sizeof(T) == 4, PlanOf<16384>::type, Plan16kD::type>::type;
+
+
+// ---- plans by length: f(Tag<PL>{}) for the plan of each family, kNoPlan when it has none ------------------------
+template <class PL>
+struct Tag {
+  using type = PL;
+};
+constexpr int kNoPlan = 1;  // (XM_OK is 0, errors are negative)
+
+#define XM_TAG_PLAN(N, NT, ...) \
+  case N:                       \
+    return f(Tag<typename PlanOf<N>::type>{});
+#define XM_TAG_ZF2(N, NT, ...) \
+  case N:                      \
+    return f(Tag<typename Zf2PlanOf<N>::type>{});
+
+template <class F>
+int plan_pow2(int n, F&& f) {
+  switch (n) {
+    XM_PLANS_POW2(XM_TAG_PLAN)
+    default: return kNoPlan;
+  }
+}
+template <class F>
+int plan_other(int n, F&& f) {
+  switch (n) {
+    XM_PLANS_OTHER(XM_TAG_PLAN)
+    default: return kNoPlan;
+  }
 }
 
-#define XM_CASE_BP(N, NT, ...) \
-  case N:                      \
-    return launch_blue<typename Zf2PlanOf<N>::type>(A, st);
+// k_zf2, half length h.  h = 4096, complex64 (the 4096 -> 8192 roofline shape): 256 threads x 16 points, radices
+// 16.16.16 -- two LDS exchanges instead of three (the exchanges run at the ds_write rate), 2 workgroups/CU
+template <class F>
+int zf2_plan(int h, F&& f) {
+  if constexpr (sizeof(T) == 4)
+    if (h == 4096) return f(Tag<typename PlanOf<4096>::type>{});
+  switch (h) {
+    XM_PLANS_ZF2(XM_TAG_ZF2)
+    default: return kNoPlan;
+  }
+}
 
-int dispatch_bluestein(int m, const PipeArgs<T>& A, hipStream_t st) {
-  static const bool no_blue = getenv("XM_NO_BLUE") != nullptr;  // tuning switch
-  if (!no_blue && A.n_batch >= 2) {
-    switch (m) {  // convolution lengths 512...4096: the persistent kernel
-      XM_PLANS_ZF2(XM_CASE_BP)
-      case 3072:  // n in (1024, 1536]: a quarter fewer flops than M = 4096, the same LDS traffic -- measured +5-9 %
-        return launch_blue<PlanBlue3072>(A, st);
-      case 8192:  // complex64: one spectrum per pass (a packed pair would need 1024 threads x 165 VGPRs)
-        if constexpr (sizeof(T) == 4) return launch_blue<typename PlanOf<8192>::type, false>(A, st);
-        break;
-      default:
-        break;
+// k_fft2 (complex64): 3*2^k / 5*2^k with 12 or 20 points per thread, radix-4 stages (2.5x / 1.6x / 2.7x k_pipe)
+template <class F>
+int fft2_plan(int n, F&& f) {
+  if constexpr (sizeof(T) == 4) {
+    switch (n) {
+      XM_PLANS_ZF2(XM_TAG_ZF2)
+      XM_PLANS_FFT2_EXTRA(XM_TAG_ZF2)
+      case 768: return f(Tag<typename PlanOf<768>::type>{});
+      case 1280: return f(Tag<typename PlanOf<1280>::type>{});
+      case 1536: return f(Tag<typename PlanOf<1536>::type>{});  // BASELINE configs[4]: 128 threads x 12 points x 2 spectra
+      case 2560: return f(Tag<typename PlanOf<2560>::type>{});
+      case 3072: return f(Tag<typename PlanOf<3072>::type>{});
+      case 5120: return f(Tag<typename PlanOf<5120>::type>{});
+      case 6144: return f(Tag<typename PlanOf<6144>::type>{});
+      default: break;
     }
   }
-  switch (m) {
-    XM_PLANS_POW2(XM_CASE_B)
-    case 3072:
-      return launch_plan<PlanBlue3072, KS_BLUESTEIN>(A, st);
-    case 16384:
-      return launch_plan<Plan16k, KS_BLUESTEIN>(A, st);
-    default:
-      break;
+  return kNoPlan;
+}
+
+// k_fft1 (complex128).  Measured (1 GiB of rows, read + write): 5.1-5.4 TB/s for 512...4096, 4.9 TB/s for 8192 (k_pipe:
+// 3.1-3.6); 512 and 4096 prefer the 8-point plans, 1024 / 2048 / 8192 the 16-point ones
+constexpr bool fft1_length(int n) {
+  return sizeof(T) == 8 && (n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 8192 || n == 768 || n == 1280 ||
+                            n == 1536 || n == 2560 || n == 3072 || n == 5120 || n == 6144);
+}
+template <class F>
+int fft1_plan(int n, F&& f) {
+  if constexpr (sizeof(T) == 8) {
+    switch (n) {
+      case 512: return f(Tag<typename Zf2PlanOf<512>::type>{});
+      case 4096: return f(Tag<typename Zf2PlanOf<4096>::type>{});
+      case 1024: return f(Tag<typename PlanOf<1024>::type>{});
+      case 2048: return f(Tag<typename PlanOf<2048>::type>{});
+      case 8192: return f(Tag<typename PlanOf<8192>::type>{});
+      case 768: return f(Tag<typename PlanOf<768>::type>{});
+      case 1280: return f(Tag<typename PlanOf<1280>::type>{});
+      case 1536: return f(Tag<typename PlanOf<1536>::type>{});
+      case 2560: return f(Tag<typename PlanOf<2560>::type>{});
+      case 3072: return f(Tag<typename PlanOf<3072>::type>{});
+      case 5120: return f(Tag<typename PlanOf<5120>::type>{});
+      case 6144: return f(Tag<typename PlanOf<6144>::type>{});
+      default: break;
+    }
   }
-  return xm_fail(XM_ERR_UNSUPPORTED_N, "no chirp-z plan of length " + std::to_string(m));
+  return kNoPlan;
+}
+
+// k_pipe: every direct plan (complex128: the lengths k_fft1 does not take, see launch())
+template <class F>
+int pipe_plan(int n, F&& f) {
+  if (n == 16384) return f(Tag<Plan16kPipe>{});
+  const int rc = plan_pow2(n, f);
+  return rc == kNoPlan ? plan_other(n, f) : rc;
+}
+
+// k_blue, convolution lengths 512...4096 and (complex64) 8192.  3072 for n in (1024, 1536]: a quarter fewer flops than
+// M = 4096, the same LDS traffic -- measured +5-9 %
+template <class F>
+int blue_plan(int m, F&& f) {
+  if (m == 3072) return f(Tag<PlanBlue3072>{});
+  if constexpr (sizeof(T) == 4)
+    if (m == 8192) return f(Tag<typename PlanOf<8192>::type>{});
+  switch (m) {
+    XM_PLANS_ZF2(XM_TAG_ZF2)
+    default: return kNoPlan;
+  }
+}
+
+// k_bluestein: the chirp-z lengths of xm_supported_in_lds
+template <class F>
+int bluestein_plan(int m, F&& f) {
+  if (m == 3072) return f(Tag<PlanBlue3072>{});
+  if (m == 16384) return f(Tag<Plan16k>{});
+  return plan_pow2(m, f);
+}
+
+// ---- the routing decision -----------------------------------------------------------------------------------------
+enum Family { F_ZF2P, F_ZF2D, F_ZF2, F_FFT2, F_FFT2_WIDE, F_FFT1, F_PIPE, F_BLUE, F_BLUESTEIN, F_BIG };
+constexpr int W = ZF2_WRITE, P = ZF2_PHASE, R = ZF2_RAMP, AM = ZF2_AMAX, VO = ZF2_VALUE_ONLY, K = ZF2_GKEY;
+
+struct Route {
+  Family family;
+  int n;                          // plan length: the half length (">= 2x zero fill"), the transform or chirp-z length
+  int mode;                       // ZF2_* words of the kernel (persistent families)
+  bool ramp;                      // the kernel applies the requested ramp itself; otherwise it is expanded into a table
+  const char* refuse = nullptr;   // the request has no kernel: why
+};
+
+// Which kernel serves a launch.  `req`: ZF2_* words of what the caller asks for -- W output, P phase table, R phase
+// ramp, AM per-row maxima, VO value-only maxima, K the launch's arg-max key.  Every special case is spelled out here.
+Route route(const void* in, int64_t in_stride, int64_t n_batch, int n_in, int n_out, int pad_left, unsigned flags,
+            int req) {
+  const bool ramp = req & R, key = req & K;
+  // the request with the ramp as a table (run() expands it when there are rows to launch on)
+  const int tab = (req & (W | P | AM)) | (ramp && n_batch > 0 ? P : 0);
+  const int h = n_out / 2, out_shift = (flags & XM_FFT_SHIFT_OUT) ? n_out / 2 : 0;
+  // ">= 2x end zero fill": the upper half of the transform input is structurally zero.  Half length 8192 (128 KB
+  // exchange buffer, middle twiddles read from L2): only k_zf2p / k_zf2d have the plan
+  bool zf2 = (xm_has_direct_plan(n_out, kDtype) || n_out == 16384) && n_out % 2 == 0 &&
+             !(flags & (XM_FFT_SHIFT_IN | XM_FFT_INVERSE)) && pad_left + n_in <= h && h >= 512 &&
+             (h <= 4096 || h == 8192) && (h == 8192 || xm_has_pow2_plan(h, kDtype)) && (out_shift == 0 || out_shift == h);
+  Route r{F_PIPE, n_out, tab, false};
+  if (sizeof(T) == 4 && zf2 && xm_pair_loads_ok(in, in_stride, n_in, pad_left)) {
+    r = {F_ZF2P, h, req & (W | P | R | AM), ramp};  // the hot kernel: packed, the ramp in closed form
+  } else if (sizeof(T) == 8 && zf2 && !(req & P) && ((req & W) ? (!(req & AM) || (req & VO)) : (req & VO)) &&
+             (h == 4096 || (h == 8192 && n_batch > 0))) {
+    r = {F_ZF2D, h, req & (W | R | AM | VO | K), ramp};  // complex128: two workgroups per CU, value-only maxima
+  } else if (zf2 && h != 8192) {  // (half length 8192 otherwise: unaligned complex64 rows, the other complex128 modes)
+    if (sizeof(T) == 8)           // the ramp in closed form; write + maxima: the variant without the index scan
+      r = {F_ZF2, h, (req & (W | P | R | AM)) | ((req & W) && (req & VO) ? VO : 0), ramp};
+    else
+      r = {F_ZF2, h, tab, false};
+  } else if (!xm_supported_in_lds(n_out, kDtype)) {
+    r = {F_BIG, n_out, tab, false};  // four-step over global memory
+  } else if (xm_has_direct_plan(n_out, kDtype)) {
+    int nt = 0;  // k_fft2 plans with at most 16 points per thread take the ramp in closed form
+    const bool fft2 = n_batch >= 2 && fft2_plan(n_out, [&](auto pl) {
+      using PL = typename decltype(pl)::type;
+      nt = PL::P <= 16 ? PL::NT : 0;
+      return XM_OK;
+    }) == XM_OK;
+    const bool native = ramp && nt > 0 && !(flags & XM_FFT_INVERSE) && out_shift % nt == 0;
+    if (fft2 && n_out == 1536 && !native && (req & W) && !(req & AM))
+      r = {F_FFT2_WIDE, n_out, tab, false};  // the plain transform (staged seam): one wave x 24 points, xm_plans.h
+    else if (fft2)
+      r = {F_FFT2, n_out, native ? req & (W | R | AM | K) : tab, native};
+    else if (fft1_length(n_out))
+      r = {F_FFT1, n_out, tab, false};
+  } else {
+    const int m = xm_bluestein_m(n_out);
+    const bool blue = n_batch >= 2 && blue_plan(m, [](auto) { return XM_OK; }) == XM_OK;
+    r = {blue ? F_BLUE : F_BLUESTEIN, m, tab, false};
+  }
+  if (!(req & W)) r.mode &= ~P;  // without an output a phase table has nothing to act on: the maxima-only kernels
+  if (key && !(r.family == F_ZF2P || r.family == F_ZF2D || (r.family == F_FFT2 && r.ramp)))
+    r.refuse = "XM_AMAX_GLOBAL_KEY on this geometry needs xm_pipeline_fused_ramp with an output and at least two rows";
+  return r;
 }
 
 int pipeline_big(PipeArgs<T> A, hipStream_t st);  // xm_bigfft.inc
 
-int pipeline_tables(PipeArgs<T>& A, int n_out, bool zf2, hipStream_t st) {
-  const int64_t n_batch = A.n_batch;
-  if (!xm_supported_in_lds(n_out, kDtype)) return pipeline_big(A, st);  // four-step over global memory
-  if (xm_has_direct_plan(n_out, kDtype)) {
-    if (zf2) {
-      const void* half = nullptr;
-      int rc = xm_table_get(TK_HALF, n_out, 0, kDtype, gen_half, nullptr, &half);
-      if (rc) return rc;
-      A.aux = (const Cx<T>*)half;
-      return dispatch_zf2(n_out / 2, A, st);
-    }
-    if constexpr (sizeof(T) == 4) {
-      static const bool no_fft2 = getenv("XM_NO_FFT2") != nullptr;  // tuning switch
-      if (!no_fft2 && n_batch >= 2) {
-        bool handled = false;
-        const int rc = dispatch_fft2(n_out, A, st, &handled);
-        if (handled) return rc;
-      }
-    }
-    if constexpr (sizeof(T) == 8) {
-      static const bool no_fft1 = getenv("XM_NO_FFT1") != nullptr;  // tuning switch
-      if (!no_fft1) {
-        bool handled = false;
-        const int rc = dispatch_fft1(n_out, A, st, &handled);
-        if (handled) return rc;
-      }
-    }
-    return dispatch_generic(n_out, A, st);
+// the kernel of a route; `ramp` = {a, b} when the route applies it natively.  (U = T: a template, so that `if constexpr`
+// discards the other precision's kernels)
+template <class U>
+int launch(const Route& r, const PipeArgs<U>& A, const double* ramp, hipStream_t st) {
+  int rc = kNoPlan;
+  switch (r.family) {
+    case F_ZF2P:
+      if constexpr (sizeof(U) == 4) return xm_zf2p_launch(r.n, r.mode, A, ramp, st);
+      break;
+    case F_ZF2D:
+      if constexpr (sizeof(U) == 8) return xm_zf2d_launch(r.n, r.mode, A, ramp, st);
+      break;
+    case F_ZF2:
+      rc = zf2_plan(r.n, [&](auto pl) {
+        using PL = typename decltype(pl)::type;
+        PipeArgs<T> B = A;
+        if (r.mode & R) xm_set_ramp<PL, true>(B, ramp);
+        auto go = [&](auto m) { return launch_zf2_mode<PL, decltype(m)::value>(B, st); };
+        if constexpr (sizeof(T) == 4)
+          return xm_with_mode<W | P | AM, W | P, W | AM, W, AM>(r.mode, go);
+        else if constexpr (PL::N == 4096)  // (k_zf2d takes the other modes of this half length)
+          return xm_with_mode<W | R | AM, W | P | AM | VO, W | P | AM, W | P, W | AM, AM>(r.mode, go);
+        else
+          return xm_with_mode<W | R | AM | VO, W | R | AM, W | R, W | P | AM | VO, W | AM | VO, W | P | AM, W | P, W | AM,
+                              W, AM>(r.mode, go);
+      });
+      break;
+    case F_FFT2:
+      rc = fft2_plan(r.n, [&](auto pl) {
+        using PL = typename decltype(pl)::type;
+        PipeArgs<T> B = A;
+        auto go = [&](auto m) { return launch_fft2_mode<PL, decltype(m)::value>(B, st); };
+        if constexpr (PL::P <= 16) {
+          if (r.mode & R) xm_set_ramp<PL, false>(B, ramp);
+          return xm_with_mode<W | R | AM | K, W | R | AM, W | R, W | P | AM, W | P, W | AM, W, AM>(r.mode, go);
+        } else {
+          return xm_with_mode<W | P | AM, W | P, W | AM, W, AM>(r.mode, go);
+        }
+      });
+      break;
+    case F_FFT2_WIDE:
+      if constexpr (sizeof(T) == 4)
+        return xm_with_mode<W | P, W>(
+            r.mode, [&](auto m) { return launch_fft2_mode<typename Plan1536Wide::type, decltype(m)::value>(A, st); });
+      break;
+    case F_FFT1:
+      rc = fft1_plan(r.n, [&](auto pl) {
+        return xm_with_mode<W | P | AM, W | P, W | AM, W, AM>(
+            r.mode, [&](auto m) { return launch_fft1_mode<typename decltype(pl)::type, decltype(m)::value>(A, st); });
+      });
+      break;
+    case F_PIPE:
+      rc = pipe_plan(r.n, [&](auto pl) {
+        using PL = typename decltype(pl)::type;
+        if constexpr (fft1_length(PL::N)) return kNoPlan;
+        else return launch_plan<PL, KS_GENERIC>(A, st);
+      });
+      break;
+    case F_BLUE:
+      rc = blue_plan(r.n, [&](auto pl) {
+        using PL = typename decltype(pl)::type;
+        constexpr bool PAIRS = sizeof(T) == 4 && PL::N != 8192;  // (8192: one spectrum per pass -- a packed pair
+                                                                 // would need 1024 threads x 165 VGPRs)
+        return xm_with_mode<W | P | AM, W | P, W | AM, W, AM>(
+            r.mode, [&](auto m) { return launch_blue_mode<PL, decltype(m)::value, PAIRS>(A, st); });
+      });
+      break;
+    case F_BLUESTEIN:
+      rc = bluestein_plan(r.n, [&](auto pl) { return launch_plan<typename decltype(pl)::type, KS_BLUESTEIN>(A, st); });
+      break;
+    case F_BIG:
+      return pipeline_big(A, st);
   }
-  const int m = xm_bluestein_m(n_out);
-  if (!xm_has_pow2_plan(m, kDtype) && m != 16384 && m != 3072)
-    return xm_fail(XM_ERR_UNSUPPORTED_N, "length " + std::to_string(n_out) + " needs a chirp-z size " +
-                                             std::to_string(m) + " beyond the in-LDS plans");
-  const void *a = nullptr, *bh = nullptr;
-  int rc = xm_table_get(TK_CHIRP, n_out, m, kDtype, gen_chirp, nullptr, &a);
+  return rc == kNoPlan ? xm_fail(XM_ERR_UNSUPPORTED_N, "no plan of length " + std::to_string(r.n)) : rc;
+}
+
+// the tables a route reads (half-length rotation, chirps, the ramp expanded into stream-ordered scratch), then its kernel
+int run(const Route& r, PipeArgs<T>& A, int n_out, const double* ramp, hipStream_t st) {
+  if (r.refuse) return xm_fail(XM_ERR_INVALID_ARG, r.refuse);
+  int rc = XM_OK;
+  const void *t1 = nullptr, *t2 = nullptr;
+  if (r.family == F_ZF2P || r.family == F_ZF2D || r.family == F_ZF2) {
+    rc = xm_table_get(TK_HALF, n_out, 0, kDtype, gen_half, nullptr, &t1);
+    A.aux = (const Cx<T>*)t1;
+  } else if (r.family == F_BLUE || r.family == F_BLUESTEIN) {
+    rc = xm_table_get(TK_CHIRP, n_out, r.n, kDtype, gen_chirp, nullptr, &t1);
+    if (!rc) rc = xm_table_get(TK_CHIRP_FFT, n_out, r.n, kDtype, gen_chirp_fft, nullptr, &t2);
+    A.aux = (const Cx<T>*)t1;
+    A.aux2 = (const Cx<T>*)t2;
+  }
   if (rc) return rc;
-  rc = xm_table_get(TK_CHIRP_FFT, n_out, m, kDtype, gen_chirp_fft, nullptr, &bh);
-  if (rc) return rc;
-  A.aux = (const Cx<T>*)a;
-  A.aux2 = (const Cx<T>*)bh;
-  return dispatch_bluestein(m, A, st);
+  if (r.ramp || !ramp || A.n_batch <= 0) return launch(r, A, r.ramp ? ramp : nullptr, st);
+  void* table = nullptr;
+  HIP_TRY(hipMallocAsync(&table, (size_t)n_out * sizeof(Cx<T>), st));
+  rc = xm_ramp_table_async(table, n_out, ramp[0], ramp[1], kDtype, st);
+  if (rc == XM_OK) {
+    A.phase = (const Cx<T>*)table;
+    rc = launch(r, A, nullptr, st);
+  }
+  HIP_TRY(hipFreeAsync(table, st));
+  return rc;
 }
 
 #include "xm_bigfft.inc"
 
-// geometry of the ">= 2x end zero-fill" fast path: the upper half of the transform input is structurally zero
-bool zf2_geometry(int n_in, int n_out, int pad_left, unsigned flags) {
-  const int h = n_out / 2;
-  const int out_shift = (flags & XM_FFT_SHIFT_OUT) ? n_out / 2 : 0;
-  return (xm_has_direct_plan(n_out, kDtype) || n_out == 16384) && (n_out % 2 == 0) && !(flags & XM_FFT_SHIFT_IN) &&
-         !(flags & XM_FFT_INVERSE) && pad_left + n_in <= h && h >= 512 &&
-         // 8192 (128 KB exchange buffer, middle twiddles read from L2): only k_zf2p / k_zf2d have the plan, the callers
-         // below fall back to the generic kernels / the long-transform path for what those do not take
-         (h <= 4096 || h == 8192) && (h == 8192 || xm_has_pow2_plan(h, kDtype)) && (out_shift == 0 || out_shift == h);
-}
-
-// k_fft2 with the ramp in closed form: complex64, a forward transform without the >= 2x zero fill, output roll a multiple
-// of the plan's thread count
-bool fft2_ramp_geometry(int n_in, int n_out, int pad_left, unsigned flags) {
-  if constexpr (sizeof(T) == 8) return false;
-  static const bool off = getenv("XM_NO_FFT2") != nullptr || getenv("XM_FFT2_TABLE") != nullptr;  // tuning switches
-  const int nt = fft2_ramp_threads(n_out);
-  if (off || nt == 0 || (flags & XM_FFT_INVERSE) || zf2_geometry(n_in, n_out, pad_left, flags)) return false;
-  const int out_shift = (flags & XM_FFT_SHIFT_OUT) ? n_out / 2 : 0;
-  return out_shift % nt == 0;
+bool ramp_native(const void* in, int64_t in_stride, int n_in, int n_out, int pad_left, unsigned flags) {
+  return route(in, in_stride, 2, n_in, n_out, pad_left, flags, W | R).ramp;
 }
 
 // the geometries whose kernel leaves the launch's arg-max in a key (XM_AMAX_GLOBAL_KEY)
 bool key_native(const void* in, int64_t in_stride, int n_in, int n_out, int pad_left, unsigned flags) {
-  if (fft2_ramp_geometry(n_in, n_out, pad_left, flags)) return true;  // k_fft2's ramp modes (round 4)
-  if (!zf2_geometry(n_in, n_out, pad_left, flags)) return false;
-  if constexpr (sizeof(T) == 8) return n_out == 8192 || n_out == 16384;  // k_zf2d's half lengths
-  PipeArgs<T> A;
-  std::memset(&A, 0, sizeof(A));
-  A.in = (const Cx<T>*)in;
-  A.n_in = n_in;
-  A.pad_left = pad_left;
-  return hot_eligible(A, in_stride);
-}
-
-bool ramp_native(const void* in, int64_t in_stride, int n_in, int n_out, int pad_left, unsigned flags) {
-  if (fft2_ramp_geometry(n_in, n_out, pad_left, flags)) return true;
-  if (!zf2_geometry(n_in, n_out, pad_left, flags)) return false;
-  if constexpr (sizeof(T) == 8) return true;  // k_zf2<double>: no alignment conditions
-  PipeArgs<T> A;
-  std::memset(&A, 0, sizeof(A));
-  A.in = (const Cx<T>*)in;
-  A.n_in = n_in;
-  A.pad_left = pad_left;
-  return hot_eligible(A, in_stride);
+  return !route(in, in_stride, 2, n_in, n_out, pad_left, flags, W | R | AM | VO | K).refuse;
 }
 
 int pipeline_typed(const void* in, int64_t in_stride, void* out, const void* window, const void* phase,
@@ -658,7 +600,7 @@ int pipeline_typed(const void* in, int64_t in_stride, void* out, const void* win
   A.out_shift = (flags & XM_FFT_SHIFT_OUT) ? n_out / 2 : 0;
   A.inverse = (flags & XM_FFT_INVERSE) ? 1 : 0;
   A.amax_value_only = (flags & XM_AMAX_VALUE_ONLY) ? 1 : 0;
-  if (flags & XM_AMAX_GLOBAL_KEY) {  // checked by the caller: complex64, value only, a geometry of the hot kernel
+  if (flags & XM_AMAX_GLOBAL_KEY) {  // checked by the caller: value only, a geometry of key_native
     A.gkey = (unsigned long long*)absmax2;
     A.key_result = (XmKeyResult*)argidx;  // may be NULL: the key is then left for xm_argmax_key_take
     A.argidx = nullptr;
@@ -670,64 +612,9 @@ int pipeline_typed(const void* in, int64_t in_stride, void* out, const void* win
   else if (flags & XM_FFT_INVERSE)
     sc = 1.0 / (double)n_out;
   A.scale = (T)sc;
-
-  bool zf2 = zf2_geometry(n_in, n_out, pad_left, flags);
-  if (sizeof(T) == 4 && zf2 && n_out == 16384 && !hot_eligible(A, in_stride)) zf2 = false;  // unaligned rows: generic kernels
-  // the hot kernel: packed complex64, applies a linear phase without a table
-  if (zf2 && hot_eligible(A, in_stride)) {
-    const void* half = nullptr;
-    int rc = xm_table_get(TK_HALF, n_out, 0, kDtype, gen_half, nullptr, &half);
-    if (rc) return rc;
-    A.aux = (const Cx<T>*)half;
-    return hot_launch(n_out / 2, A, ramp, st);
-  }
-  if constexpr (sizeof(T) == 8) {
-    if (zf2 && n_out == 16384) {  // half length 8192: k_zf2d's modes or nothing (-> the long-transform path)
-      bool handled = false;
-      if (n_batch > 0) {
-        const void* half = nullptr;
-        int rc = xm_table_get(TK_HALF, n_out, 0, kDtype, gen_half, nullptr, &half);
-        if (rc) return rc;
-        A.aux = (const Cx<T>*)half;
-        rc = zf2d_launch(n_out / 2, A, ramp, st, &handled);
-        if (handled) return rc;
-        A.aux = nullptr;
-      }
-      zf2 = false;
-    }
-    // complex128 twin of the hot kernel: k_zf2 with the ramp in closed form
-    static const bool table_only = getenv("XM_ZF2D_TABLE") != nullptr;  // tuning switch
-    if (zf2 && ramp && out && n_batch > 0 && !table_only) {
-      const void* half = nullptr;
-      int rc = xm_table_get(TK_HALF, n_out, 0, kDtype, gen_half, nullptr, &half);
-      if (rc) return rc;
-      A.aux = (const Cx<T>*)half;
-      return dispatch_zf2(n_out / 2, A, st, ramp);
-    }
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (ramp && out && n_batch >= 2 && fft2_ramp_geometry(n_in, n_out, pad_left, flags)) {
-      bool handled = false;
-      const int rc = dispatch_fft2(n_out, A, st, &handled, ramp);
-      if (handled) return rc;
-    }
-    if (A.gkey && fft2_ramp_geometry(n_in, n_out, pad_left, flags))  // (k_fft2 knows the key in its ramp form only)
-      return xm_fail(XM_ERR_INVALID_ARG, "XM_AMAX_GLOBAL_KEY on this geometry needs xm_pipeline_fused_ramp with an output and at least two rows");
-  }
-  // every other kernel takes the phase as a table: a ramp is expanded into stream-ordered scratch memory first
-  void* ramp_table = nullptr;
-  if (ramp && n_batch > 0) {
-    HIP_TRY(hipMallocAsync(&ramp_table, (size_t)n_out * sizeof(Cx<T>), st));
-    int rc = xm_ramp_table_async(ramp_table, n_out, ramp[0], ramp[1], kDtype, st);
-    if (rc) {
-      (void)hipFreeAsync(ramp_table, st);
-      return rc;
-    }
-    A.phase = (const Cx<T>*)ramp_table;
-  }
-  const int rc = pipeline_tables(A, n_out, zf2, st);
-  if (ramp_table) HIP_TRY(hipFreeAsync(ramp_table, st));
-  return rc;
+  const int req = (out ? W : 0) | (phase ? P : 0) | (ramp ? R : 0) | (absmax2 ? AM : 0) |
+                  (absmax2 && A.amax_value_only ? VO : 0) | (A.gkey ? K : 0);
+  return run(route(in, in_stride, n_batch, n_in, n_out, pad_left, flags, req), A, n_out, ramp, st);
 }
 
 }  // namespace

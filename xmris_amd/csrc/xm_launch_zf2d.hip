@@ -45,43 +45,19 @@ int launch_mode(PipeArgs<T> A, hipStream_t st) {
   return XM_OK;
 }
 
-template <class PL, int MODE>
-int launch_mode_dma(const PipeArgs<T>& A, hipStream_t st) {
-  static const bool no_dma = getenv("XM_ZF2D_NODMA") != nullptr;  // tuning switch: the next row is not prefetched
-  return no_dma ? launch_mode<PL, MODE>(A, st) : launch_mode<PL, MODE | ZF2_DMA>(A, st);
-}
-
 template <class PL>
-int launch_plan(PipeArgs<double> A, const double* ramp, hipStream_t st) {
-  const bool wr = A.out != nullptr, am = A.absmax2 != nullptr, key = A.gkey != nullptr;
-  constexpr int AM = ZF2_AMAX | ZF2_VALUE_ONLY, AMK = AM | ZF2_GKEY;
-  if (!wr) return key ? launch_mode_dma<PL, AMK>(A, st) : launch_mode_dma<PL, AM>(A, st);
-  if (ramp) {
-    // e^{i (a + b k)}, k = base_q + 2t (+1): the wave-uniform factors, and e^{i b} for the odd bins (xm_zf2p.h)
-    constexpr unsigned N = 2 * PL::N;
-    for (int q = 0; q < PL::P; ++q) {
-      const unsigned base = (2u * PL::NT * q + (unsigned)A.out_shift) & (N - 1u);
-      const double a = ramp[0] + ramp[1] * (double)base;
-      A.ramp_c[2 * q] = std::cos(a);
-      A.ramp_c[2 * q + 1] = std::sin(a);
-    }
-    A.ramp_e[0] = std::cos(ramp[1]);
-    A.ramp_e[1] = std::sin(ramp[1]);
-    A.ramp_db = ramp[1];
-    if (key) return launch_mode_dma<PL, ZF2_WRITE | ZF2_RAMP | AMK>(A, st);
-    return am ? launch_mode_dma<PL, ZF2_WRITE | ZF2_RAMP | AM>(A, st) : launch_mode_dma<PL, ZF2_WRITE | ZF2_RAMP>(A, st);
-  }
-  if (key) return launch_mode_dma<PL, ZF2_WRITE | AMK>(A, st);
-  return am ? launch_mode_dma<PL, ZF2_WRITE | AM>(A, st) : launch_mode_dma<PL, ZF2_WRITE>(A, st);
+int launch_plan(PipeArgs<T> A, int mode, const double* ramp, hipStream_t st) {
+  if (mode & ZF2_RAMP) xm_set_ramp<PL, true>(A, ramp);
+  constexpr int W = ZF2_WRITE, R = ZF2_RAMP, AM = ZF2_AMAX | ZF2_VALUE_ONLY, K = AM | ZF2_GKEY;
+  // (every mode prefetches the next row into the idle exchange buffer: ZF2_DMA)
+  return xm_with_mode<AM, K, W, W | AM, W | K, W | R, W | R | AM, W | R | K>(
+      mode, [&](auto m) { return launch_mode<PL, decltype(m)::value | ZF2_DMA>(A, st); });
 }
 
 }  // namespace
 
-int xm_zf2d_launch(int h, const PipeArgs<double>& A, const double* ramp, hipStream_t st, bool* handled) {
-  static const bool gen1 = getenv("XM_ZF2D_GEN1") != nullptr;  // tuning switch: k_zf2<double> / the long-transform path
-  const bool wr = A.out != nullptr, ph = A.phase != nullptr, am = A.absmax2 != nullptr;
-  *handled = !gen1 && !ph && (wr ? (!am || A.amax_value_only) : (am && A.amax_value_only)) && (h == 4096 || h == 8192);
-  if (!*handled) return XM_OK;
-  if (h == 4096) return launch_plan<typename PlanOf<4096>::type>(A, ramp, st);  // 256 threads x 16 points, 16.16.16
-  return launch_plan<typename Zf2PlanOf<8192>::type>(A, ramp, st);               // 1024 threads x 8 points, 8.8.8.8.2
+int xm_zf2d_launch(int h, int mode, const PipeArgs<double>& A, const double* ramp, hipStream_t st) {
+  if (h == 4096) return launch_plan<typename PlanOf<4096>::type>(A, mode, ramp, st);  // 256 threads x 16 points, 16.16.16
+  if (h == 8192) return launch_plan<typename Zf2PlanOf<8192>::type>(A, mode, ramp, st);  // 1024 threads x 8 points, 8.8.8.8.2
+  return xm_fail(XM_ERR_UNSUPPORTED_N, "no half-length plan for " + std::to_string(h));
 }

@@ -297,10 +297,8 @@ struct Pool {
 
   // test hook (XM_SOLVER_TEST_STALL="<member>,<microseconds>"): that member sleeps before every 5th job it takes
   int stall_id = -1, stall_us = 0;
-  bool no_backup = false;  // tuning switch XM_SOLVER_NO_BACKUP: wait for every member however long it takes (round 2)
   Pool() {
     if (const char* e = std::getenv("XM_SOLVER_TEST_STALL")) std::sscanf(e, "%d,%d", &stall_id, &stall_us);
-    no_backup = std::getenv("XM_SOLVER_NO_BACKUP") != nullptr;
   }
 
   bool in_use = false;  // guarded by g_pools_mu
@@ -399,7 +397,7 @@ struct Pool {
       backed_up[w] = false;
       const uint64_t grace = suspect[w] ? kSuspectGraceCycles : kGraceCycles;
       while (slot[w].ack.load(std::memory_order_acquire) != g) {
-        if (!no_backup && __rdtsc() - t0 > grace) {  // not there: its share is a few microseconds of the caller's time
+        if (__rdtsc() - t0 > grace) {  // not there: its share is a few microseconds of the caller's time
           run_share(jb, w, backup.data() + (size_t)w * 5 * kMaxLocal);
           backed_up[w] = suspect[w] = true;
           backups.fetch_add(1, std::memory_order_relaxed);
@@ -486,7 +484,7 @@ void* xm_solver_create(const double* slice_re_im, const double* coords, int n, d
   s->du = (s->u[n - 1] - s->u[0]) / (double)(n - 1);
   double dev = 0;
   for (int k = 0; k < n; ++k) dev = std::max(dev, std::fabs(s->u[k] - (s->u[0] + (double)k * s->du)));
-  s->uniform = dev <= 4e-15 && !std::getenv("XM_SOLVER_NO_RECURRENCE");
+  s->uniform = dev <= 4e-15;
   return s;
 }
 

@@ -60,13 +60,10 @@ constexpr int xm_ilog2(int v) {
 }
 
 // pad shift of the exchange buffer (one pad element per 2^shift elements; -1: the block FFT's default)
-#ifndef ZF2P_SH8
-#define ZF2P_SH8 4
-#endif
 template <class PL, bool L16>
 constexpr int zf2p_pad_shift() {
   if (!L16) return -1;
-  return PL::radix(0) == 8 ? ZF2P_SH8 : xm_ilog2(2 * PL::radix(0));
+  return PL::radix(0) == 8 ? 4 : xm_ilog2(2 * PL::radix(0));
 }
 
 template <class PL, int MODE, int OPT>
