@@ -221,6 +221,30 @@ int64_t xm_baseline_als_workspace_bytes(int64_t n_batch, int n);
 int xm_baseline_als(const void* in, int is_complex, int64_t n_batch, int n, double lam, double p, int n_iter, void* out,
                     void* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- quantification: AMARES time-domain fitting (reference fitting/amares.py:207-488, fitting/simulation.py:9-96).
+ * Model: x^(t) = sum_k a_k e^{i phi_k} exp(-d_k (1 - g_k + g_k t) t) e^{i 2 pi f_k t}, t_j = j dt + t0.  Parameters of
+ * peak k are params[5k + c], c = 0 amplitude, 1 frequency [Hz], 2 damping [1/s], 3 phase [rad], 4 lineshape g; fp64.
+ *
+ * xm_amares_model: out[b, j] (complex128) = x^(t_j) for the parameters params[b, :, :] ([n_batch, n_peaks, 5]). */
+int xm_amares_model(const double* params, int64_t n_batch, int n_peaks, int n, double dt, double t0, void* out,
+                    void* stream);
+/* xm_amares_fit: one Levenberg-Marquardt fit per row of `in` (n_batch rows of n complex samples, dtype XM_C64 / XM_C128,
+ * `in_row_stride` elements apart) in lmfit's internal bound variables, every row from the same start.  Prior
+ * knowledge: HOST arrays of 5 n_peaks values -- `init` (clipped into its bounds), `lower` / `upper` (+-inf: unbounded
+ * side), `fixed` (nonzero, or lower == upper: held at its value, not fitted).  Stops when the scaled step
+ * ||D d|| <= xtol (||D u|| + xtol), the relative cost reduction of an accepted step is <= ftol, or after max_iter trial
+ * steps.  Outputs (device): params[n_batch, n_peaks, 5] physical, amp_sd[n_batch, n_peaks] = sqrt of the amplitude's
+ * diagonal entry of (J^T J)^{-1} over the physical free parameters at the solution (the caller scales it by sigma;
+ * 0 for a fixed amplitude, NaN when J^T J is singular), rss[n_batch] = sum |x - x^|^2, status[n_batch] (0 converged,
+ * 1 iteration cap, 2 non-finite: params, amp_sd and fit_data zero, rss NaN), iters[n_batch]; `fit_data` (may be NULL):
+ * [n_batch, n] complex128 model at the solution.  `workspace`: xm_amares_workspace_bytes() bytes of device memory.
+ * n_peaks in 1 ... 16, n >= free parameters. */
+int64_t xm_amares_workspace_bytes(int64_t n_batch, int n, int n_peaks);
+int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, double dt, double t0, int n_peaks,
+                  const double* init, const double* lower, const double* upper, const int32_t* fixed, int max_iter,
+                  double ftol, double xtol, double* params, double* amp_sd, double* rss, int32_t* status,
+                  int32_t* iters, void* fit_data, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

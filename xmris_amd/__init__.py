@@ -10,6 +10,7 @@ __version__ = "0.4.0"
 from . import _lib  # noqa: F401
 from .accessor import XmrisAccessor, register_xarray_accessor
 from .config import ATTRS, COORDS, DIMS
+from .fitting import fit_amares, simulate_fid
 from .fused import spectral_pipeline
 from .labeled import Coordinate, LabeledArray
 from .vendor.bruker import remove_digital_filter
@@ -20,5 +21,5 @@ DataArray = LabeledArray  # convenience alias for code written against xarray's 
 register_xarray_accessor()  # no-op when xarray is absent or the name `xmr` is already owned
 
 __all__ = ["baseline_als", "ATTRS", "COORDS", "DIMS", "Coordinate", "DataArray", "LabeledArray", "XmrisAccessor",
-           "apodize_exp", "apodize_lg", "autophase", "fft", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
-           "phase", "register_xarray_accessor", "remove_digital_filter", "spectral_pipeline", "to_fid", "to_spectrum", "zero_fill"]
+           "apodize_exp", "apodize_lg", "autophase", "fft", "fit_amares", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
+           "phase", "register_xarray_accessor", "remove_digital_filter", "simulate_fid", "spectral_pipeline", "to_fid", "to_spectrum", "zero_fill"]

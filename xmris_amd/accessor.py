@@ -88,7 +88,19 @@ class XmrisFusedMixin:
                                  method=method, peak_width=peak_width, **kwargs)
 
 
-class XmrisAccessor(XmrisFourierMixin, XmrisProcessingMixin, XmrisPhasingMixin, XmrisVendorMixin, XmrisFusedMixin):
+class XmrisFittingMixin:
+    def fit_amares(self, prior_knowledge_file, dim: str = "time", mhz: float = None, sw: float = None,
+                   deadtime: float = None, method: str = "leastsq", initialize_with_lm: bool = True,
+                   num_workers: int = 4, init_fid=None, verbose: bool = False):
+        from .fitting.amares import fit_amares
+
+        return fit_amares(self._obj, prior_knowledge_file, dim=dim, mhz=mhz, sw=sw, deadtime=deadtime, method=method,
+                          initialize_with_lm=initialize_with_lm, num_workers=num_workers, init_fid=init_fid,
+                          verbose=verbose)
+
+
+class XmrisAccessor(XmrisFourierMixin, XmrisProcessingMixin, XmrisPhasingMixin, XmrisVendorMixin, XmrisFusedMixin,
+                    XmrisFittingMixin):
     """``obj.xmr.<method>`` for the hot-path methods."""
 
     def __init__(self, obj):

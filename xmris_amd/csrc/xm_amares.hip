@@ -1,0 +1,156 @@
+// Host side of the AMARES entry points (xm_amares_* in include/xmris_hip.h); kernels in xm_amares.h.
+#include "xm_host.h"
+#include "xm_amares.h"
+
+#include <cmath>
+#include <string>
+
+static int am_fail(const std::string& msg) { return xm_fail(XM_ERR_INVALID_ARG, "amares: " + msg); }
+
+namespace {
+// the device that owns `ptr` is current for the duration of a call (see the conventions in xmris_hip.h)
+struct AmDeviceGuard {
+  int prev = -1;
+  explicit AmDeviceGuard(const void* ptr) {
+    hipPointerAttribute_t at;
+    if (!ptr || hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+      (void)hipGetLastError();
+      return;
+    }
+    int cur = 0;
+    if (at.type != hipMemoryTypeDevice || hipGetDevice(&cur) != hipSuccess) return;
+    if (cur != at.device && hipSetDevice(at.device) == hipSuccess) prev = cur;
+  }
+  ~AmDeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+XmResidency g_am_res;
+
+int am_q_pts(int lda) {  // points per staging round: 128, 64 or 32 so that 2 q lda doubles fit the staging budget
+  int q = 128;
+  while (q > 32 && 2 * (size_t)q * lda * sizeof(double) > XM_AM_STAGE_BYTES) q >>= 1;
+  return q;
+}
+
+size_t am_lds_bytes(int P, int lda, int q) {
+  return ((size_t)P * P + 7 * (size_t)P + 2 * XM_AM_MAXQ + XM_AM_NT + 2 * (size_t)q * lda) * sizeof(double);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t xm_amares_workspace_bytes(int64_t n_batch, int n, int n_peaks) {
+  (void)n_batch;
+  (void)n;
+  (void)n_peaks;
+  return 256;  // the row counter pair
+}
+
+int xm_amares_model(const double* params, int64_t n_batch, int n_peaks, int n, double dt, double t0, void* out,
+                    void* stream) {
+  if (n_batch < 0 || n < 1 || n_peaks < 1 || n_peaks > XM_AM_MAXK) return am_fail("model: needs n >= 1, 1 <= n_peaks <= 16");
+  if (n_batch > 0 && (!params || !out)) return am_fail("model: null pointer");
+  if (!std::isfinite(dt) || !std::isfinite(t0)) return am_fail("model: dt and t0 must be finite");
+  if (n_batch == 0) return XM_OK;
+  AmDeviceGuard guard(out);
+  const long long total = (long long)n_batch * n;
+  long long blocks = (total + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(k_amares_model, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params,
+                     (long long)n_batch, n_peaks, n, dt, t0, (double*)out);
+  HIP_TRY(hipGetLastError());
+  return XM_OK;
+}
+
+int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, double dt, double t0, int n_peaks,
+                  const double* init, const double* lower, const double* upper, const int32_t* fixed, int max_iter,
+                  double ftol, double xtol, double* params, double* amp_sd, double* rss, int32_t* status,
+                  int32_t* iters, void* fit_data, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+  if (n_peaks < 1 || n_peaks > XM_AM_MAXK) return am_fail("n_peaks must be in 1 ... 16");
+  if (n_batch < 0 || n < 1 || in_row_stride < n) return am_fail("needs n_batch >= 0, n >= 1, row stride >= n");
+  if (dtype != XM_C64 && dtype != XM_C128) return am_fail("dtype must be XM_C64 or XM_C128");
+  if (!init || !lower || !upper || !fixed) return am_fail("null prior-knowledge pointer");
+  if (n_batch > 0 && (!in || !params || !amp_sd || !rss || !status || !iters || !workspace))
+    return am_fail("null pointer");
+  if (workspace_bytes < xm_amares_workspace_bytes(n_batch, n, n_peaks))
+    return am_fail("workspace too small (see xm_amares_workspace_bytes)");
+  if (max_iter < 1 || !(ftol >= 0.0) || !(xtol >= 0.0)) return am_fail("needs max_iter >= 1, ftol >= 0, xtol >= 0");
+  if (!(dt > 0.0) || !std::isfinite(dt) || !std::isfinite(t0)) return am_fail("dt must be positive and finite, t0 finite");
+  if (n_batch > 0xffffffffLL) return am_fail("n_batch too large (> 2^32 - 1)");
+
+  AmaresFitArgs A{};
+  A.x = in;
+  A.stride = in_row_stride;
+  A.nb = n_batch;
+  A.n = n;
+  A.is_c64 = dtype == XM_C64;
+  A.dt = dt;
+  A.t0 = t0;
+  A.K = n_peaks;
+  A.max_iter = max_iter;
+  A.ftol = ftol;
+  A.xtol = xtol;
+  // bounds and the internal start values (HOST arrays of 5 n_peaks values: the prior knowledge is shared by the batch)
+  int P = 0;
+  for (int q = 0; q < 5 * n_peaks; ++q) {
+    const double lo = lower[q], hi = upper[q];
+    if (std::isnan(lo) || std::isnan(hi) || lo > hi || !std::isfinite(init[q]))
+      return am_fail("parameter " + std::to_string(q) + ": bounds must satisfy lo <= hi, initial value finite");
+    const double v = std::fmin(std::fmax(init[q], lo), hi);  // initial values are clipped into their bounds
+    A.lo[q] = lo;
+    A.hi[q] = hi;
+    if (fixed[q] || lo == hi) {
+      if (!std::isfinite(v)) return am_fail("parameter " + std::to_string(q) + ": a fixed value must be finite");
+      A.bt[q] = XM_AM_FIXED;
+      A.col[q] = -1;
+      A.u0[q] = v;
+      continue;
+    }
+    A.col[q] = (signed char)P++;
+    const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
+    if (fl && fh) {
+      A.bt[q] = XM_AM_TWO;
+      A.u0[q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
+    } else if (fl) {
+      A.bt[q] = XM_AM_LO;
+      A.u0[q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
+    } else if (fh) {
+      A.bt[q] = XM_AM_HI;
+      A.u0[q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
+    } else {
+      A.bt[q] = XM_AM_FREE;
+      A.u0[q] = v;
+    }
+  }
+  if (P < 1) return am_fail("every parameter is fixed");
+  if (n < P) return am_fail("n (" + std::to_string(n) + ") smaller than the free parameters (" + std::to_string(P) + ")");
+  if (n_batch == 0) return XM_OK;
+
+  A.P = P;
+  A.lda = P + 1;
+  A.q_pts = am_q_pts(A.lda);
+  A.params = params;
+  A.asd = amp_sd;
+  A.rss = rss;
+  A.status = status;
+  A.iters = iters;
+  A.fit = (double*)fit_data;
+  A.counter = (unsigned*)workspace;
+
+  AmDeviceGuard guard(in);
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
+  const size_t lds = am_lds_bytes(P, A.lda, A.q_pts);
+  int resident = 0;
+  const int rc = xm_resident_blocks(g_am_res, k_amares_fit, XM_AM_NT, lds, &resident, st);
+  if (rc) return rc;
+  const long long blocks = n_batch < resident ? n_batch : resident;
+  xm_note_kernel("k_amares_fit", nullptr, nullptr, P, -1);
+  hipLaunchKernelGGL(k_amares_fit, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
+  HIP_TRY(hipGetLastError());
+  return XM_OK;
+}
+
+}  // extern "C"

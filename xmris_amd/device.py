@@ -313,6 +313,70 @@ def baseline_als(x, axis: int, lam: float, p: float, n_iter: int):
     return restore(out)
 
 
+def amares_model(params, n: int, dt: float, t0: float):
+    """AMARES model (fitting/simulation.py:9-96): params [..., K, 5] fp64 device tensor (a, f [Hz], d [1/s], phi [rad],
+    g per peak) -> complex128 FIDs [..., n] at t_j = j dt + t0."""
+    torch = _torch()
+    _require_device(params)
+    p = params.to(torch.float64).contiguous()
+    if p.dim() < 2 or p.shape[-1] != 5:
+        raise ValueError(f"amares_model needs parameters [..., n_peaks, 5], got {tuple(p.shape)}")
+    lead, k = tuple(p.shape[:-2]), p.shape[-2]
+    nb = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    out = torch.empty(lead + (n,), dtype=torch.complex128, device=p.device)
+    _lib.call("xm_amares_model", p.data_ptr(), nb, k, int(n), float(dt), float(t0), out.data_ptr(), _stream(p))
+    return out
+
+
+class AmaresFit:
+    """Raw outputs of ``amares_fit`` with the non-time axes of the input in front: params [..., K, 5] (fitting units),
+    amp_sd [..., K] (sqrt of the amplitude's diagonal entry of (J^T J)^-1, not yet scaled by sigma), rss [...],
+    status [...] (0 converged, 1 iteration cap, 2 non-finite), iters [...], fit [..., n] complex128 (or None)."""
+
+    __slots__ = ("params", "amp_sd", "rss", "status", "iters", "fit", "n_free")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, max_iter: int = 200,
+               ftol: float = 1e-10, xtol: float = 1e-10, want_fit: bool = True) -> AmaresFit:
+    """One Levenberg-Marquardt AMARES fit per FID along `axis` of the complex64 / complex128 device tensor `x`, all
+    voxels in one launch (xm_amares_fit).  init / lo / hi / fixed: [K, 5] prior knowledge in fitting units (a, f [Hz],
+    d [1/s], phi [rad], g), shared by every voxel."""
+    torch = _torch()
+    _require_device(x)
+    code = _dtype_code(x)
+    init, lo, hi = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1, 5)) for v in (init, lo, hi))
+    fixed = np.ascontiguousarray(np.asarray(fixed, dtype=bool).reshape(-1, 5).astype(np.int32))
+    k = init.shape[0]
+    if not (lo.shape == hi.shape == fixed.shape == init.shape):
+        raise ValueError("init, lo, hi and fixed must all be [n_peaks, 5]")
+    axis = axis % x.dim()
+    x2, restore = _rows(x, axis)
+    nb, n = x2.shape
+    lead = tuple(s for i, s in enumerate(x.shape) if i != axis)
+    dev_ = x.device
+    params = torch.empty((nb, k, 5), dtype=torch.float64, device=dev_)
+    asd = torch.empty((nb, k), dtype=torch.float64, device=dev_)
+    rss = torch.empty(nb, dtype=torch.float64, device=dev_)
+    status = torch.empty(nb, dtype=torch.int32, device=dev_)
+    iters = torch.empty(nb, dtype=torch.int32, device=dev_)
+    fit = torch.empty((nb, n), dtype=torch.complex128, device=dev_) if want_fit else None
+    need = int(_lib.load().xm_amares_workspace_bytes(nb, n, k))
+    work = torch.zeros(max(need, 8), dtype=torch.uint8, device=dev_)
+    ptr = lambda a: a.ctypes.data  # noqa: E731  (host prior-knowledge arrays)
+    _lib.call("xm_amares_fit", x2.data_ptr(), n, nb, n, float(dt), float(t0), k, ptr(init), ptr(lo), ptr(hi), ptr(fixed),
+              int(max_iter), float(ftol), float(xtol), params.data_ptr(), asd.data_ptr(), rss.data_ptr(),
+              status.data_ptr(), iters.data_ptr(), fit.data_ptr() if fit is not None else None, work.data_ptr(), need,
+              code, _stream(x))
+    n_free = int(np.count_nonzero(~(fixed.astype(bool) | (lo == hi))))
+    return AmaresFit(params=params.reshape(lead + (k, 5)), amp_sd=asd.reshape(lead + (k,)), rss=rss.reshape(lead),
+                     status=status.reshape(lead), iters=iters.reshape(lead),
+                     fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
