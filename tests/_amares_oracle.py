@@ -170,3 +170,227 @@ def p31_workload(n_vox, n=2048, sw=10000.0, mhz=120.0, seed=0, noise=0.5):
     data = np.stack([model(truth[v], t) for v in range(n_vox)])
     data = data + noise * (rng.standard_normal(data.shape) + 1j * rng.standard_normal(data.shape))
     return data, truth, t
+
+
+# ---- pieces that judge the kernel away from the converged solution (tests/test_amares_kernel.py) ---------------------
+def _split(lo, hi, fixed, init=None):
+    lo, hi = (np.asarray(v, dtype=np.float64).ravel() for v in (lo, hi))
+    fixed = np.zeros(lo.size, bool) if fixed is None else np.asarray(fixed, bool).ravel()
+    fixed = fixed | (lo == hi)
+    return lo, hi, fixed, np.flatnonzero(~fixed)
+
+
+def real_rows(z):
+    """complex [n, ...] -> real [2n, ...]: real parts, then imaginary parts (the 2n real residuals of n points)."""
+    return np.concatenate([z.real, z.imag])
+
+
+def start_values(init, lo, hi, fixed=None):
+    """(v0, u0): the start clipped into the bounds (all 5K parameters) and the internal start of the free ones."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    v0 = np.clip(np.asarray(init, dtype=np.float64).ravel(), lo, hi)
+    return v0, np.array([to_internal(v0[q], lo[q], hi[q]) for q in free])
+
+
+def physical(u, v0, lo, hi, fixed=None):
+    """(p, s): all 5K physical values and slopes dp/du at the internal vector u; fixed parameters keep v0, slope 0."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    p, s = np.array(v0, dtype=np.float64).ravel().copy(), np.zeros(lo.size)
+    for j, q in enumerate(free):
+        p[q], s[q] = from_internal(u[j], lo[q], hi[q])
+    return p, s
+
+
+def _normal(x, t, p, scale, free):
+    jr = real_rows(model_jacobian(p, t)[:, free] * scale)
+    r = real_rows(np.asarray(x, dtype=np.complex128) - model(p, t))
+    return jr.T @ jr, jr.T @ r, float(r @ r), jr, r
+
+
+def normal_equations(x, t, params, lo, hi, fixed=None, internal=False):
+    """(H, g, F) at the physical point `params` over the free columns: H = J^T J, g = J^T r, F = |r|^2 with
+    r = x - model (2n real residuals) and J = d model / d parameter -- so that the Gauss-Newton step solves H delta = g.
+    internal: J with respect to the internal variables, i.e. chained through from_internal's slope at
+    u = to_internal(params)."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    p = np.asarray(params, dtype=np.float64).ravel()
+    scale = np.ones(free.size)
+    if internal:
+        scale = np.array([from_internal(to_internal(p[q], lo[q], hi[q]), lo[q], hi[q])[1] for q in free])
+    return _normal(x, t, p, scale, free)[:3]
+
+
+def amplitude_sd(t, params, lo, hi, fixed=None):
+    """(sd [K], cond): sqrt(diag((J^T J)^{-1})) of the amplitudes over the physical free columns at `params` (0 for a
+    fixed amplitude), from an SVD of the column-scaled Jacobian, and the 2-norm condition number of the unscaled
+    J^T J (what the kernel factors)."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    jr = real_rows(model_jacobian(params, t)[:, free])
+    sv = np.linalg.svd(jr, compute_uv=False)
+    with np.errstate(divide="ignore"):
+        cond = float((sv[0] / sv[-1]) ** 2) if sv[-1] > 0 else np.inf
+    c = np.linalg.norm(jr, axis=0)
+    sd = np.zeros(lo.size)
+    if np.all(c > 0):
+        _, s, vt = np.linalg.svd(jr / c, full_matrices=False)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sd[free] = np.sqrt(np.sum((vt.T / s) ** 2, axis=1)) / c
+    else:
+        sd[free] = np.nan
+    return sd.reshape(-1, 5)[:, 0], cond
+
+
+def lm_steps(x, t, init, lo, hi, fixed=None, max_iter=200, ftol=1e-10, xtol=1e-10, solver="normal"):
+    """The iteration of DESIGN.md section 8, restated: Levenberg-Marquardt in the internal variables from the clipped
+    start; lambda_0 = 1e-3; D_j the largest squared column norm so far (1 for an always-zero column); a trial solves
+    (H + lambda D) delta = g; accepted when the cost falls, then lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2;
+    rejected (also when the system cannot be solved): lambda *= nu, nu *= 2.  Stops: |sqrt(D) delta| <=
+    xtol (|sqrt(D) u| + xtol) (tested on every trial), or an accepted step reduces the cost by <= ftol relative; the
+    trial cap leaves status 1.  `iters` counts trials.
+
+    solver: "normal" -- numpy.linalg.solve on the fp64 normal equations; "qr" -- least squares (LAPACK, orthogonal
+    factorisation) on the augmented Jacobian [J; sqrt(lambda D)], which never forms J^T J.
+
+    Returns a dict: params [K, 5], u, rss, iters, status, trials (list of (accepted, (F - Ft) / F)), path [5K] (the sum
+    of |change| of every parameter over the accepted steps: the scale in which two trajectories are compared)."""
+    x = np.asarray(x, dtype=np.complex128)
+    t = np.asarray(t, dtype=np.float64)
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    v0, u = start_values(init, lo, hi, fixed)
+    P = free.size
+    p, s = physical(u, v0, lo, hi, fixed)
+    r = x - model(p, t)
+    F = float(np.sum(r.real ** 2 + r.imag ** 2))
+    dsc = np.zeros(P)
+    lam, nu, it = 1e-3, 2.0, 0
+    status = 1 if np.isfinite(F) else 2
+    need_jac, trials, path = True, [], np.zeros(lo.size)
+    while status == 1 and it < max_iter:
+        if need_jac:
+            p, s = physical(u, v0, lo, hi, fixed)
+            H, g, _, jr, rr = _normal(x, t, p, s[free], free)
+            dsc = np.maximum(dsc, np.diag(H))
+            need_jac = False
+        it += 1
+        D = np.where(dsc > 0, dsc, 1.0)
+        try:
+            with np.errstate(all="ignore"):
+                if solver == "qr":
+                    a = np.concatenate([jr, np.diag(np.sqrt(lam * D))])
+                    dl = np.linalg.lstsq(a, np.concatenate([rr, np.zeros(P)]), rcond=None)[0]
+                else:
+                    dl = np.linalg.solve(H + lam * np.diag(D), g)
+            ok = bool(np.all(np.isfinite(dl)))
+        except np.linalg.LinAlgError:
+            ok = False
+        if not ok:
+            trials.append((False, -np.inf))
+            lam *= nu
+            nu *= 2.0
+            if not np.isfinite(lam):
+                break
+            continue
+        dn = np.sqrt(np.sum(D * dl * dl))
+        un = np.sqrt(np.sum(D * u * u))
+        pred = float(dl @ (lam * D * dl + g))
+        xconv = dn <= xtol * (un + xtol)
+        ut = u + dl
+        pt, _ = physical(ut, v0, lo, hi, fixed)
+        with np.errstate(all="ignore"):
+            rt = x - model(pt, t)
+            Ft = float(np.sum(rt.real ** 2 + rt.imag ** 2))
+        margin = (F - Ft) / F if F > 0 and np.isfinite(Ft) else -np.inf
+        if np.isfinite(Ft) and Ft < F:
+            trials.append((True, margin))
+            rho = min(max((F - Ft) / pred, 0.0), 1.0)
+            fconv = (F - Ft) <= ftol * F
+            path += np.abs(pt - p)
+            u, F, p = ut, Ft, pt
+            q = 2.0 * rho - 1.0
+            lam *= max(1.0 / 3.0, 1.0 - q * q * q)
+            nu = 2.0
+            need_jac = True
+            if fconv or xconv:
+                status = 0
+        else:
+            trials.append((False, margin))
+            lam *= nu
+            nu *= 2.0
+            if xconv:
+                status = 0
+            if not np.isfinite(lam):
+                break
+    p = physical(u, v0, lo, hi, fixed)[0]
+    if not (np.all(np.isfinite(p)) and np.isfinite(F)):
+        status = 2
+    return {"params": p.reshape(-1, 5), "u": u, "rss": F, "iters": it, "status": status, "trials": trials,
+            "path": path}
+
+
+def kernel_case(K, n, seed, dt=1e-4, t0=5e-4, noise=0.2, n_vox=1, fix_g=False, fix_phase=False, on_bound=()):
+    """Seeded K well-separated Voigt peaks with dead time and noise, a start perturbed away from the truth and bounds
+    of all four types: amplitude lower-only (0, inf); frequency two-sided (+-60 Hz); damping upper-only (-inf, 400) on
+    even peaks and lower-only (2, inf) on odd ones; phase unbounded on even peaks and two-sided (-pi, pi) on odd ones;
+    g two-sided (0, 1).  n_vox voxels share truth and prior knowledge and differ in their noise.
+    fix_g: g held through fixed[] at its start value; fix_phase: phases held through lo == hi.
+    on_bound: (peak, column, "lo" | "hi") triples whose start value is put exactly on that bound.
+    Only cases whose J^T J (physical, at the truth) has 64 eps cond <= 1e-4 are emitted: a seed that misses is
+    re-drawn deterministically.  Records shorter than 25 ms cannot meet that (the peaks have hardly decayed: cond is
+    4e10 at K = 1, n = 80) and are emitted as drawn.  Returns a dict: x [n_vox, n] complex128, t, dt, t0, truth, init, lo, hi, fixed [K, 5]."""
+    t = np.arange(n) * dt + t0
+    for attempt in range(50):
+        rng = np.random.default_rng([seed, K, n, attempt])
+        truth = np.zeros((K, 5))
+        truth[:, 0] = rng.uniform(5.0, 20.0, K)
+        centre = np.linspace(-3500.0, 3500.0, K) if K > 1 else np.zeros(1)
+        truth[:, 1] = centre + rng.uniform(-20.0, 20.0, K)
+        truth[:, 2] = rng.uniform(30.0, 90.0, K)
+        truth[:, 3] = rng.uniform(-0.5, 0.5, K)
+        truth[:, 4] = rng.uniform(0.2, 0.8, K)
+        init = truth.copy()
+        init[:, 0] *= rng.uniform(0.8, 1.2, K)
+        init[:, 1] += rng.uniform(-4.0, 4.0, K)
+        init[:, 2] *= rng.uniform(0.85, 1.15, K)
+        init[:, 3] += rng.uniform(-0.2, 0.2, K)
+        init[:, 4] = np.clip(truth[:, 4] + rng.uniform(-0.15, 0.15, K), 0.1, 0.9)
+        lo, hi = np.full((K, 5), -np.inf), np.full((K, 5), np.inf)
+        lo[:, 0] = 0.0
+        lo[:, 1], hi[:, 1] = centre - 60.0, centre + 60.0
+        hi[0::2, 2] = 400.0
+        lo[1::2, 2] = 2.0
+        lo[1::2, 3], hi[1::2, 3] = -np.pi, np.pi
+        lo[:, 4], hi[:, 4] = 0.0, 1.0
+        fixed = np.zeros((K, 5), bool)
+        if fix_g:
+            fixed[:, 4] = True
+            init[:, 4] = truth[:, 4]
+        if fix_phase:
+            lo[:, 3] = hi[:, 3] = init[:, 3] = truth[:, 3]
+        for k, c, side in on_bound:
+            init[k, c] = lo[k, c] if side == "lo" else hi[k, c]
+        z = rng.standard_normal((n_vox, n)) + 1j * rng.standard_normal((n_vox, n))
+        x = model(truth, t)[None] + noise * z
+        if n * dt < 0.025 or 64 * np.finfo(np.float64).eps * amplitude_sd(t, truth, lo, hi, fixed)[1] <= 1e-4:
+            break
+    else:
+        raise RuntimeError(f"kernel_case({K}, {n}, {seed}): no well-conditioned draw")
+    return {"x": x, "t": t, "dt": dt, "t0": t0, "truth": truth, "init": init, "lo": lo, "hi": hi, "fixed": fixed}
+
+
+def step_cases():
+    """(name, kernel_case arguments) of the cases on which the first trial steps are compared one by one: every staging
+    tier at a ragged record length, and two 2-peak cases in which parameters of every bounded type start exactly on a
+    bound (the others start inside)."""
+    return [
+        ("K1_n257", dict(K=1, n=257, seed=31, n_vox=2)),
+        ("K6_n1000", dict(K=6, n=1000, seed=32, n_vox=2)),
+        ("K7_n1000", dict(K=7, n=1000, seed=33, n_vox=2)),
+        ("K13_n1500", dict(K=13, n=1500, seed=34, n_vox=2)),
+        ("K16_n3001", dict(K=16, n=3001, seed=35, n_vox=2)),
+        ("K16_fixed_g_n1000", dict(K=16, n=1000, seed=36, n_vox=2, fix_g=True)),
+        # frequency (two-sided) on hi, damping (upper only) on hi, phase (two-sided) on lo, g (two-sided) on lo
+        ("K2_on_bound_a", dict(K=2, n=700, seed=37, n_vox=2,
+                               on_bound=((1, 1, "hi"), (0, 2, "hi"), (1, 3, "lo"), (0, 4, "lo")))),
+        # amplitude (lower only) on lo, damping (lower only) on lo, g (two-sided) on hi
+        ("K2_on_bound_b", dict(K=2, n=700, seed=38, n_vox=2, on_bound=((0, 0, "lo"), (1, 2, "lo"), (1, 4, "hi")))),
+    ]

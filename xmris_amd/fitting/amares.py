@@ -66,7 +66,9 @@ def fit_amares(da, prior_knowledge_file, dim: str = "time", mhz: float | None = 
     sigma = np.sqrt(rss / (2 * n - res.n_free))[..., None]
     amp = params[..., 0]
     with np.errstate(divide="ignore", invalid="ignore"):
-        crlb = np.where(amp != 0, 100.0 * res.amp_sd.cpu().numpy() * sigma / np.abs(amp), 0.0)
+        asd = res.amp_sd.cpu().numpy()
+        crlb = np.where(amp != 0, 100.0 * asd * sigma / np.abs(amp), 0.0)
+        crlb = np.where(np.isnan(asd), np.nan, crlb)  # singular J^T J: the bound is undefined, whatever the amplitude
         snr = np.where(sigma > 0, amp / sigma, 0.0)
     values = {"amplitude": amp, "chem_shift": params[..., 1] / mhz, "linewidth": params[..., 2] / np.pi,
               "phase": np.rad2deg(params[..., 3]), "crlb": crlb, "snr": snr}
