@@ -389,6 +389,24 @@ def test_xarray_bridge_through_a_test_double(oracle, monkeypatch):
         labeled.as_labeled(np.zeros(3))
 
 
+def _sweep_spectrum(aps, seed):
+    """Spectrum `seed` of the divergence sweep: (spectrum, frequency axis, pivot, arg-max index, index width)."""
+    n, sw = 2048, 5000.0
+    t = np.arange(n) / sw
+    freq = np.roll(np.fft.fftfreq(n, d=1 / sw), n // 2)
+    rng = np.random.default_rng(1000 + seed)
+    k = int(rng.integers(3, 6))
+    fid = np.zeros(n, complex)
+    for _ in range(k):
+        fid += rng.uniform(0.3, 1.0) * np.exp(-rng.uniform(15.0, 60.0) * t) * np.exp(2j * np.pi * rng.uniform(-2000, 2000) * t)
+    fid += 0.01 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    spec = np.roll(np.fft.fft(fid * np.exp(-np.pi * 3.0 * t), norm="ortho"), n // 2)
+    kmax = int(np.argmax(np.abs(spec)))
+    pivot = float(freq[kmax])
+    spec = spec * np.exp(1j * aps.phase_angles(freq, rng.uniform(-150, 150), rng.uniform(-600, 600), pivot))
+    return spec, freq, pivot, kmax, aps.index_width_of(freq, 100)
+
+
 def test_native_search_vs_scipy_divergence_sweep():
     """How often does the native search end somewhere else than the reference's route
     (scipy.optimize.differential_evolution on the numpy objective, phasing.py:276-284)?  60 seeded spectra of 3-5
@@ -406,23 +424,10 @@ def test_native_search_vs_scipy_divergence_sweep():
     polish="native" (what round 3's streaming executor ran) is measured beside it and only held to contract (iii)."""
     from xmris_amd import autophase_solver as aps
 
-    n, sw = 2048, 5000.0
-    t = np.arange(n) / sw
-    freq = np.roll(np.fft.fftfreq(n, d=1 / sw), n // 2)
     stats = {m: dict(n=0, identical=0, polished=0, route_numpy=0, dp0=0.0, dp1=0.0, dfun=0.0, native_dp0=0.0, native_dp1=0.0)
              for m in aps.METHODS}
     for seed in range(60):
-        rng = np.random.default_rng(1000 + seed)
-        k = int(rng.integers(3, 6))
-        fid = np.zeros(n, complex)
-        for _ in range(k):
-            fid += rng.uniform(0.3, 1.0) * np.exp(-rng.uniform(15.0, 60.0) * t) * np.exp(2j * np.pi * rng.uniform(-2000, 2000) * t)
-        fid += 0.01 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
-        spec = np.roll(np.fft.fft(fid * np.exp(-np.pi * 3.0 * t), norm="ortho"), n // 2)
-        kmax = int(np.argmax(np.abs(spec)))
-        pivot = float(freq[kmax])
-        spec = spec * np.exp(1j * aps.phase_angles(freq, rng.uniform(-150, 150), rng.uniform(-600, 600), pivot))
-        iw = aps.index_width_of(freq, 100)
+        spec, freq, pivot, kmax, iw = _sweep_spectrum(aps, seed)
         method = aps.METHODS[seed % 3]
         p0n, p1n, on = aps.solve(spec, freq, pivot, kmax, iw, method=method, engine="native")  # polish="exact"
         p0s, p1s, os_ = aps.solve(spec, freq, pivot, kmax, iw, method=method, engine="scipy")
@@ -444,6 +449,55 @@ def test_native_search_vs_scipy_divergence_sweep():
         assert (ov.fun - os_.fun) / max(abs(os_.fun), floor * 1e7) <= 1e-7, (seed, method, ov.fun, os_.fun)
     print("native vs scipy route per method:", stats)
     assert stats["acme"]["identical"] >= stats["acme"]["n"] - stats["acme"]["polished"]
+
+
+def test_reference_polish_is_public_minimize_on_the_public_scores_to_the_bit():
+    """`polish_reference` -- the one polish on the reference's route, whoever asks for it (a single accessor call, the
+    streaming executor, a worker process): the lean L-BFGS-B driver on the objective object.  It must be what
+    `differential_evolution` does for the reference (phasing.py:276-284): the public `scipy.optimize.minimize` on the
+    public score function, then scipy's acceptance rule -- identical x, fun, nfev and accepted flag.  The 60 spectra
+    of the divergence sweep, every method, one and two parameters, a seeded random start each; every method must accept
+    a polish that iterated (otherwise nothing was compared but the start)."""
+    import scipy.optimize
+
+    from xmris_amd import autophase_solver as aps
+
+    iterated = {m: 0 for m in aps.METHODS}
+    for seed in range(60):
+        spec, freq, pivot, kmax, iw = _sweep_spectrum(aps, seed)
+        rng = np.random.default_rng(5000 + seed)
+        start = np.array([rng.uniform(-180, 180), rng.uniform(-4000, 4000)])
+        for method, fn in (("acme", aps.acme_score), ("peak_minima", aps.peak_minima_score), ("positivity", aps.roi_positivity_score)):
+            args = (spec, freq, pivot) + (() if method == "acme" else (kmax, iw))
+            for p0_only in (False, True):
+                bounds = [(-180.0, 180.0)] if p0_only else [(-180.0, 180.0), (-4000.0, 4000.0)]
+                x0 = start[:len(bounds)]
+                fun0 = float(fn(x0, *args))
+                ref = scipy.optimize.minimize(fn, np.copy(x0), args=args, method="L-BFGS-B", bounds=bounds)
+                accepted = bool(ref.fun < fun0 and ref.success and all(lo <= v <= hi for v, (lo, hi) in zip(ref.x, bounds)))
+                want_x, want_fun = (ref.x, float(ref.fun)) if accepted else (x0, fun0)
+                x, fun, nfev, polished = aps.polish_reference(spec, freq, pivot, kmax, iw, method, p0_only, np.copy(start))
+                tag = (seed, method, p0_only)
+                assert np.array_equal(x, want_x) and fun == want_fun and nfev == ref.nfev and polished == accepted, tag
+                iterated[method] += int(accepted and ref.nit >= 1)
+    print("accepted polishes that iterated, of 120 per method:", iterated)
+    assert all(v >= 1 for v in iterated.values()), iterated
+
+
+def test_polish_worker_child_imports_neither_torch_nor_the_hip_library():
+    """A polish worker is numpy, scipy and the objective statements: importing its module (what the child's
+    `python -c` does) and the objective it serves must leave torch out of `sys.modules` and libxmris_hip / the HIP
+    runtime out of the process's loaded libraries."""
+    import subprocess
+    import sys
+
+    code = ("import sys; from xmris_amd import polish_workers as w; from xmris_amd import autophase_solver\n"
+            "assert callable(w.main) and 'torch' not in sys.modules, sorted(m for m in sys.modules if 'torch' in m)\n"
+            "libs = [ln.split()[-1] for ln in open('/proc/self/maps') if 'libxmris_hip' in ln or 'libamdhip' in ln]\n"
+            "assert not libs, libs\n")
+    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert res.returncode == 0, res.stderr[-2000:]
 
 
 def test_deferred_chain_metadata_matches_materialised_data(monkeypatch):
@@ -575,7 +629,7 @@ def test_winner_spectrum_is_the_reference_slice_bit_for_bit(oracle, dtype, n_in,
 
 
 def test_polish_workers_never_make_a_caller_wait_for_their_start(oracle):
-    """`autophase_solver.PolishWorkers`: a request submitted before any worker has reported ready is polished by the
+    """`polish_workers.PolishWorkers` (children: `polish_workers.main`): a request submitted before any worker has reported ready is polished by the
     future's own thread; once the workers are up they answer with the same (x, fun, nfev) to the bit -- the polish is
     the reference's route either way (phasing.py:276-284 with scipy's defaults) -- and a worker that dies is replaced by
     the in-thread polish, not waited for."""
@@ -662,7 +716,7 @@ def test_polish_falls_back_to_public_minimize_when_scipy_internals_change(oracle
         real_setulb = _lbfgsb.setulb
 
         def setulb(*args, **kwargs):  # scipy 1.17's C rewrite takes other arguments than this package passes
-            if sys._getframe(1).f_globals.get("__name__") == aps.__name__:
+            if sys._getframe(1).f_globals.get("__name__") == aps.polish_lbfgsb.__module__:
                 raise TypeError("setulb() takes 12 positional arguments but 17 were given")
             return real_setulb(*args, **kwargs)  # (scipy's own front end knows its own core)
 
@@ -825,11 +879,12 @@ def test_solver_team_budget(monkeypatch):
     the searches in flight on the node (16 CPUs, 8 ranks: 8 -- round 2's rule left one thread); few cores per rank ->
     blocking event waits."""
     from xmris_amd import autophase_solver as aps
+    from xmris_amd import cpu_budget
 
     for var in ("XM_SOLVER_THREADS", "XM_BLOCKING_SYNC", "LOCAL_WORLD_SIZE"):
         monkeypatch.delenv(var, raising=False)
     share = {"n": 16}
-    monkeypatch.setattr(aps, "_cpu_share", lambda: share["n"])
+    monkeypatch.setattr(cpu_budget, "cpu_share", lambda: share["n"])
     assert (aps.default_threads(), aps.burst_threads(), aps.scarce_cpus()) == (8, 16, False)
     # a streaming call: three quarters of the share for two searches in flight (each busy half of its two device
     # periods), half of it when the host paces the steps (every team spins all the time)

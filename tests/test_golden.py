@@ -32,7 +32,13 @@ def test_host_solver_matches_golden_scores_and_solution():
 
     g = _load("scores.npz")
     sl, fr, pv, ti, iw = g["slice"], g["freq"], float(g["pivot"]), int(g["target_idx"]), int(g["index_width"])
+    objective = {m: aps.NumpyObjective(sl, fr, pv, ti, iw, m) for m in aps.METHODS}
     for i, p in enumerate(g["points"]):
+        # the objective object (what the polish walks) and the public function: one set of statements, the same float
+        for q in (p, p[:1]):
+            assert objective["acme"](q) == aps.acme_score(q, sl, fr, pv)
+            assert objective["peak_minima"](q) == aps.peak_minima_score(q, sl, fr, pv, ti, iw)
+            assert objective["positivity"](q) == aps.roi_positivity_score(q, sl, fr, pv, ti, iw)
         assert aps.acme_score(p, sl, fr, pv) == pytest.approx(g["acme"][i], rel=1e-13)
         assert aps.peak_minima_score(p, sl, fr, pv, ti, iw) == pytest.approx(g["peak_minima"][i], rel=1e-12, abs=1e-15)
         assert aps.roi_positivity_score(p, sl, fr, pv, ti, iw) == pytest.approx(g["positivity"][i], rel=1e-12)

@@ -125,13 +125,13 @@ def test_auto_engine_rule(monkeypatch, cpus, ranks, gpus, want_device):
     _stream_double.install(monkeypatch)
     import torch
 
-    from xmris_amd import autophase_solver as aps
+    from xmris_amd import cpu_budget
     from xmris_amd import pipeline as pl
 
     monkeypatch.setenv("XM_SOLVER_THREADS", "2")
     monkeypatch.delenv("XMRIS_AMD_SEARCH", raising=False)
     monkeypatch.setenv("LOCAL_WORLD_SIZE", str(ranks))
-    monkeypatch.setattr(aps, "_CPU_SHARE", cpus)
+    monkeypatch.setattr(cpu_budget, "_CPU_SHARE", cpus)
     monkeypatch.setattr(torch.cuda, "device_count", lambda: gpus)
     for k in _stream_double.COUNTS:
         _stream_double.COUNTS[k] = 0

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import autophase_solver as aps
 from . import device as dev
+from .cpu_budget import search_team as _search_team, search_workers as _search_workers  # noqa: F401 -- the policy's home
 from .dims import MSG_POSITION
 
 
@@ -258,7 +259,7 @@ def run(x2, t, target_points: int, lb: float, method: str = "acme", peak_width=1
     import torch
 
     if polish is None:
-        polish = os.environ.get("XMRIS_AMD_POLISH", "exact")
+        polish = aps.default_polish()
 
     if plan is None:
         plan = make_plan(x2, t, target_points, lb)
@@ -328,9 +329,7 @@ def run_stream(inputs, outputs, plan: PipelinePlan, *, exchange=None, broadcast=
 
     n_sets = len(inputs)
     if polish is None:
-        import os
-
-        polish = os.environ.get("XMRIS_AMD_POLISH", "exact")
+        polish = aps.default_polish()
     if n_sets != len(outputs):
         raise ValueError("inputs and outputs must have the same length")
     if n_sets == 0:
@@ -429,48 +428,6 @@ def _run_stream(inputs, outputs, plan, exchange, broadcast, rank_offset_rows, ov
         if trace is not None:
             trace.append(ev)
     return results
-
-
-# measured speed-up of one host search with a team of 1 / 2 / 4 / 8 / 16 threads
-_SPEEDUP = {1: 1.0, 2: 1.73, 4: 3.05, 8: 4.25, 16: 5.7}
-
-
-def _search_ms(n_out: int, threads: int) -> float:
-    """Host search time (ms) with a team of `threads` (n_out = 8192, ACME: 3.2 / 1.9 / 1.1 / 0.76 ms of generations with
-    1 / 2 / 4 / 8 threads + 0.3 ms of polish; generations scale with n_out)."""
-    gain = _SPEEDUP[max(k for k in _SPEEDUP if k <= max(1, threads))]
-    return 0.3 + 3.2 * (n_out / 8192.0) / gain
-
-
-def _search_workers(plan: PipelinePlan, n_rows: int, elem_bytes: int, threads: int | None = None):
-    """(searches in flight, threads per search) for the streaming executor.  A search is O(1) per dataset on the host
-    (`_search_ms`); the device period is the dataset's compulsory traffic at ~5.5 TB/s plus ~0.12 ms of small launches.
-    Three searches at a time with a third of the team each where that keeps up with the device; otherwise four with a
-    quarter each (a smaller team spends fewer core-milliseconds per search).  Measured (16-CPU share; ms per step with
-    2 / 4 / 8 in flight): 16,384 x 2048 -> 4096: 0.73 / 0.60 / 0.79, 32,768 x 1536: 0.49 / 0.47 / 0.66, 65,536 x 4096
-    -> 8192: 1.17 / 1.19 / 1.23 -- eight single-thread searches lose to the interpreter lock (every search ends in
-    scipy's polish, ~0.3 ms of Python)."""
-    def team_of(w):  # an explicit budget (tests, tuning) is divided evenly
-        return max(1, threads // w) if given else _search_team(w)
-
-    given = threads is not None
-    if not given:
-        threads = aps.stream_threads()
-    device_ms = n_rows * (plan.n_in + plan.n_out) * elem_bytes / 5.5e9 + 0.12
-    # THREE in flight where the device paces the steps (teams of four out of twelve threads): a search then has three
-    # device periods, ~2 ms of slack instead of ~1 for a search that runs late (a contended host), at the same
-    # throughput on a quiet one -- six A/B pairs at K = 20: 51.7 vs 51.4 M spectra/s, three at K = 100: 55.35 vs
-    # 55.20, 5.7 instead of 6.8 cores busy.
-    w = 3
-    if _search_ms(plan.n_out, max(1, threads // w)) / w > 0.8 * device_ms and threads >= 4:
-        w = 4
-    return w, team_of(w)
-
-
-def _search_team(workers: int) -> int:
-    """Threads per search with `workers` searches in flight (`autophase_solver.stream_threads`: more than three in
-    flight means the host paces the steps)."""
-    return max(1, aps.stream_threads(host_paced=workers > 3) // max(1, workers))
 
 
 def phase_ramp_of(plan: PipelinePlan, p0: float, p1: float, pivot: float):

@@ -26,9 +26,9 @@ import torch
 
 from . import _lib
 from . import autophase_solver as aps
+from . import cpu_budget
 from . import device as dev
-from .pipeline import (AutophaseResult, Selection, _search_ms, _search_team, _search_workers, main_pass, slice_on_host,
-                       winner_spectrum)
+from .pipeline import AutophaseResult, Selection, main_pass, slice_on_host, winner_spectrum
 
 _SUB_STEP = 8  # the L1 guess reads every 8th 1-KiB block of the samples it uses (see `Schedule`)
 
@@ -65,7 +65,7 @@ class Schedule:
     several ranks the order of the exchange calls must be the same on every rank: the order-fixing fields are then
     derived from rank 0's broadcast values and from nothing a rank measures or owns."""
 
-    workers: int      # searches in flight (`_search_workers`)
+    workers: int      # searches in flight (`cpu_budget.search_workers`)
     team: int         # threads per search in flight
     fill_team: int    # threads of the pipeline-filling search
     n_workers: int    # searches RUNNING side by side (more may be queued)
@@ -108,13 +108,13 @@ def _device_engine_wanted(plan, method, polish, overlap) -> bool:
     profiles/r03/rehearsal_6ranks.txt), and only where every rank has a GPU of its own (see below)."""
     want = os.environ.get("XMRIS_AMD_SEARCH", "auto")
     if want == "auto":
-        local_world = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+        local_world = cpu_budget.local_world()
         # (a GPU of its own: the partition is made of CU-masked queues, and those of several processes on ONE card
         # reserve the same CUs and oversubscribe its hardware queues -- six ranks sharing a GPU fell into the
         # scheduler's 10.7 ms process time slices, 124 instead of 1.4 ms per step, profiles/r04/rehearsal_6ranks.txt;
         # four ranks still ran at full speed)
         own_gpu = torch.cuda.device_count() >= local_world
-        want = "device" if (aps._cpu_share() < 2 * local_world and own_gpu) else "host"
+        want = "device" if (cpu_budget.cpu_share() < 2 * local_world and own_gpu) else "host"
     axis = _uniform_axis(plan)
     return (want == "device" and polish == "exact" and method == "acme" and overlap and axis is not False
             and dev.search_supported(plan.n_out, method, axis[2]))
@@ -170,7 +170,7 @@ def _guess_n_used(plan) -> int:
 
 def make_schedule(inputs, plan, exchange, broadcast, overlap, method, polish) -> Schedule:
     n_sets, n, x0 = len(inputs), plan.n_out, inputs[0]
-    workers, _ = _search_workers(plan, x0.shape[0], x0.element_size())
+    workers, _ = cpu_budget.search_workers(plan, x0.shape[0], x0.element_size())
     use_dev = _device_engine_wanted(plan, method, polish, overlap)
     # ~600 objective evaluations; measured per evaluation: 2.3 us + 0.4 us per 1000 bins (profiles/r04/device_search.txt)
     est_ms = 600 * (2.3 + 0.4 * n / 1000.0) * 1e-3
@@ -213,17 +213,17 @@ def make_schedule(inputs, plan, exchange, broadcast, overlap, method, polish) ->
     use_guess = (os.environ.get("XM_GUESS_L1") is None and plan.window is not None
                  and all(_geometry(plan, x)[1] for x in distinct))
     return Schedule(
-        workers=workers, team=_search_team(n_workers) if n_workers else aps.stream_threads(),
+        workers=workers, team=cpu_budget.search_team(n_workers) if n_workers else cpu_budget.stream_threads(),
         # the pipeline-filling search (the first main pass waits for it) takes the whole CPU share for its
         # millisecond: four A/B pairs at the driver's K = 20: 53.1 -> 53.8 M spectra/s
-        fill_team=aps.burst_threads(), n_workers=n_workers, s_ahead=s_ahead, s_look=s_look, g_ahead=g_ahead,
+        fill_team=cpu_budget.burst_threads(), n_workers=n_workers, s_ahead=s_ahead, s_look=s_look, g_ahead=g_ahead,
         ring=g_ahead + 2, cpu_fill=cpu_fill, use_dev=use_dev, dev_ahead=dev_ahead, est_ms=est_ms, fast_fill=fast_fill,
         # (the ramp, measured through the multi-rank code path on a GPU of its own, profiles/r04/fill.txt: 1.302 ->
         # 1.244 ms per step against the whole look-ahead in front of the first main pass)
         ramped=overlap and not use_dev and not fast_fill,
         use_service=polish == "exact", use_keys=use_keys, use_guess=use_guess,
         l1_keys=use_keys and not c128 and not use_guess,  # the L1 guess stage leaves its winner in a key (complex64)
-        band=_guess_band(plan), n_used=_guess_n_used(plan), sub_step=_SUB_STEP, blocking=aps.scarce_cpus())
+        band=_guess_band(plan), n_used=_guess_n_used(plan), sub_step=_SUB_STEP, blocking=cpu_budget.scarce_cpus())
 
 
 # ---- buffers -----------------------------------------------------------------------------------------------------
@@ -348,10 +348,10 @@ class Hedger:
     def deadline(self, i: int, t_exchanged: float, scale: float, offset: float = 0.0) -> float:
         """When dataset i's search counts as late.  Without a history of three searches -- with several ranks a rank
         only searches the datasets it owns, so it may never have one (found by the eight-rank executor test) -- the
-        cost model stands in, generously: `scale` x `_search_ms` + `offset` (seconds)."""
+        cost model stands in, generously: `scale` x `cpu_budget.search_ms` + `offset` (seconds)."""
         recent = (self.fill_hist if i == 0 else self.run_hist)[-9:]
         if len(recent) < 3:
-            recent = [scale * _search_ms(self.n_out, self.fill_team if i == 0 else self.team) + offset]
+            recent = [scale * cpu_budget.search_ms(self.n_out, self.fill_team if i == 0 else self.team) + offset]
         typical = sorted(recent)[len(recent) // 2]
         return t_exchanged + 2.0 * typical + 0.5e-3
 
@@ -365,7 +365,7 @@ class PolishHandoff:
     """Searches that do not pass scipy's projected-gradient test are polished on the reference's route (numpy
     objective, milliseconds of interpreter): a helper starts on that as soon as the search's record says so -- the
     launch thread looks at the records of the searches in flight once per dataset -- instead of the launch thread
-    doing it when it needs the result.  The helper is a worker PROCESS (`autophase_solver.PolishWorkers`): a polish is
+    doing it when it needs the result.  The helper is a worker PROCESS (`polish_workers.PolishWorkers`): a polish is
     milliseconds of small numpy operations, and on helper THREADS they were taken out of this thread's share of the
     interpreter lock -- on the heterogeneous family, where 13 searches of 16 need the polish, the launch thread fell
     from 1.4 to 2.3 ms per dataset (profiles/r04/hetero_polish.txt).  XM_POLISH_THREADS=n keeps them on threads."""
