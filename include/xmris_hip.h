@@ -281,6 +281,16 @@ int xm_solver_de(void* solver, int p0_only, unsigned seed, double tol, int maxit
  * pinned staging buffer for xm_phase_apply / xm_pipeline_fused).  Returns 0, or -1 for bad arguments. */
 int xm_phase_table(const double* coords, int n, double p0_deg, double p1_deg, double pivot, void* out, int as_float);
 
+/* A8 with one ramp per row (`autophase_each`): out[r, k] = in[r, k] e^{i phi}, phi = rad(p0[r]) + rad(p1[r]) *
+ * (coords[k] - pivot[r]) / (max coords - min coords), the statements of phasing.py:56-73 in fp64 (a zero range gives
+ * phi = rad(p0[r])).  `coords` (n doubles, any axis, uniform or not), `p0` / `p1` (degrees) / `pivot` (n_rows doubles
+ * each) and `skip` (NULL, or n_rows int32: nonzero rows are copied through unchanged, whatever their p0 / p1 / pivot
+ * hold) are DEVICE arrays; data XM_C64 / XM_C128, contiguous rows, in == out allowed.  The angle of every bin is the
+ * reference's to the bit; a thread takes sincos once per eight consecutive bins and turns from bin to bin by the
+ * angle's exact difference (a short series; differences above 1/4 rad take sincos again). */
+int xm_phase_apply_rows(const void* in, void* out, const double* coords, int64_t n_rows, int n, const double* p0,
+                        const double* p1, const double* pivot, const int32_t* skip, int dtype, void* stream);
+
 /* ---- A7 on the device: the (p0, p1) search of processing/phasing.py:276-284 for the ACME objective (:100-122) as ONE
  * workgroup beside the streaming kernels (csrc/xm_search.hip): scipy 1.15.3's differential evolution for the
  * reference's configuration (seed -> numpy RandomState stream, latin hypercube, best1bin, dither U[0.5, 1), CR 0.7,
@@ -316,6 +326,31 @@ int xm_search_launch(const void* slice, int n, double c0, double cstep, double x
  * `xs` / `fs` device-accessible. */
 int xm_search_eval(const void* slice, int n, double c0, double cstep, double x_range, int target_idx, int p0_only,
                    const double* xs, int count, double* fs, void* stream);
+
+/* ---- A7 for every spectrum of a dataset (`autophase_each`): the search above for each row of in[n_rows, n] (XM_C64 /
+ * XM_C128, contiguous rows, read only; samples are widened to fp64 on load), one workgroup per row over all CUs of
+ * `stream` (rows go round the resident workgroups by a grid stride).  Each row's search is the same function of its
+ * samples as a lone xm_search_launch.  `pivot`: NaN -- every row's pivot is the coordinate of its first arg-max of |X|
+ * (`target_idx` must be -1); otherwise that pivot for every row, with `target_idx` the bin nearest to it
+ * (phasing.py:233-235).  `records`: n_rows records in plain device memory, complete when the stream reaches the
+ * launch's end (no sequence word).  A row without a search -- all bins zero, or a sample that is not finite: the ACME
+ * score is 0/0 there -- ends before the first evaluation with x, fun, pg_norm = NaN and its own status.
+ * Support is xm_search_supported's: ACME (method 0), a uniform axis with x_range > 0, 2 <= n <= 16576. */
+enum { XM_SEARCH_CONVERGED = 0, XM_SEARCH_MAXITER = 1, XM_SEARCH_ALL_ZERO = 2, XM_SEARCH_NOT_FINITE = 3 };
+typedef struct {
+  double x[2];          /* p0, p1 in degrees (p1 = 0 with p0_only)                                     */
+  double fun;           /* objective at x                                                               */
+  double pg_norm;       /* projected-gradient norm at x, as in xm_search_result                         */
+  int32_t nfev, nit;    /* evaluations and generations (the gradient test's are not counted)            */
+  int32_t target_idx;   /* the target bin: first arg-max of |row|, or the one given (-1: not finite)    */
+  int32_t status;       /* XM_SEARCH_*                                                                  */
+  int32_t needs_polish; /* 1: the caller polishes on the reference's route (see xm_search_result)       */
+  int32_t pad_;
+} xm_search_row;
+int xm_search_rows_supported(int n, int method, double x_range, int dtype);
+int xm_search_rows(const void* in, int64_t n_rows, int n, int dtype, double c0, double cstep, double x_range, int p0_only,
+                   unsigned seed, double tol, int maxiter, double pivot, int target_idx, xm_search_row* records,
+                   void* stream);
 
 /* ---- A7 on the host without the interpreter: the same search -- xm_solver_de's generations, then the projected-
  * gradient test of the polish (xm_solver_fg) -- run by a native thread of the library's search service; `out` (HOST

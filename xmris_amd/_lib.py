@@ -80,6 +80,10 @@ SIGNATURES = {
     "xm_search_launch": (_i, [_p, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _i, _u, ctypes.c_double, _i,
                               ctypes.c_uint64, _p, _p]),
     "xm_search_eval": (_i, [_p, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _i, _p, _i, _p, _p]),
+    "xm_search_rows_supported": (_i, [_i, _i, ctypes.c_double, _i]),
+    "xm_search_rows": (_i, [_p, _l, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _u, ctypes.c_double, _i,
+                            ctypes.c_double, _i, _p, _p]),
+    "xm_phase_apply_rows": (_i, [_p, _p, _p, _l, _i, _p, _p, _p, _p, _i, _p]),
     "xm_hostsearch_submit": (_i, [_p, _i, _p, _i, _i, _i, _i, _u, ctypes.c_double, _i, _i, ctypes.c_uint64, _p]),
     "xm_hostsearch_set_workers": (_i, [_i]),
     "xm_stream_create": (_i, [_p, _i, _i]),

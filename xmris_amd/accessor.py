@@ -12,7 +12,7 @@ from __future__ import annotations
 from .config import DIMS
 from .processing.fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .processing.fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
-from .processing.phasing import autophase, phase
+from .processing.phasing import autophase, autophase_each, phase
 from .dims import _check_dims  # noqa: F401  (the reference re-exports it from its accessor module)
 
 
@@ -68,6 +68,13 @@ class XmrisPhasingMixin:
         # reference (accessor.py:634 vs phasing.py:166)
         return autophase(self._obj, dim=dim, method=method, peak_width=peak_width, lb=lb,
                          temp_time_dim=temp_time_dim, **kwargs)
+
+
+    def autophase_each(self, dim: str = DIMS.frequency, method: str = "acme", peak_width: int = 100,
+                       lb: float = 0.0, temp_time_dim: str = DIMS.time, **kwargs):
+        """One (p0, p1) per spectrum along `dim` (an addition of this backend: the reference's ``mode="all"``)."""
+        return autophase_each(self._obj, dim=dim, method=method, peak_width=peak_width, lb=lb,
+                              temp_time_dim=temp_time_dim, **kwargs)
 
 
 class XmrisVendorMixin:

@@ -481,6 +481,27 @@ int xm_phase_apply(const void* in, void* out, const void* phase_table, int64_t n
   return XM_OK;
 }
 
+int xm_phase_apply_rows(const void* in, void* out, const double* coords, int64_t n_rows, int n, const double* p0,
+                        const double* p1, const double* pivot, const int32_t* skip, int dtype, void* stream) {
+  int rc = check_common(in, n_rows, n, dtype);
+  if (rc) return rc;
+  if (n_rows == 0) return XM_OK;
+  if (!out || !coords || !p0 || !p1 || !pivot) return fail(XM_ERR_INVALID_ARG, "phase_apply_rows: null pointer");
+  const long long tiles = ((long long)n + kPhaseRowsBins * kPhaseRowsThreads - 1) / (kPhaseRowsBins * kPhaseRowsThreads);
+  long long grid = (long long)n_rows * tiles;
+  if (grid > 256LL * 8) grid = 256LL * 8;  // 256 CUs x 8 resident workgroups, the rest by a grid stride
+  hipStream_t st = (hipStream_t)stream;
+  DeviceGuard guard(in);
+  if (dtype == XM_C64)
+    hipLaunchKernelGGL(k_phase_rows<float>, dim3((unsigned)grid), dim3(kPhaseRowsThreads), 0, st, (const Cx<float>*)in,
+                       (Cx<float>*)out, coords, (long long)n_rows, n, p0, p1, pivot, (const int*)skip);
+  else
+    hipLaunchKernelGGL(k_phase_rows<double>, dim3((unsigned)grid), dim3(kPhaseRowsThreads), 0, st, (const Cx<double>*)in,
+                       (Cx<double>*)out, coords, (long long)n_rows, n, p0, p1, pivot, (const int*)skip);
+  HIP_TRY(hipGetLastError());
+  return XM_OK;
+}
+
 int xm_roll(const void* in, void* out, int64_t n_batch, int n, int shift, int dtype, void* stream) {
   int rc = check_common(in, n_batch, n, dtype);
   if (rc) return rc;

@@ -7,6 +7,7 @@
 //   k_bluestein : arbitrary length through a power-of-two chirp-z convolution, same fused I/O.
 //   elementwise : zero_fill, apodize, phase, roll, per-row arg-max, final arg-max.
 #pragma once
+#include <cfloat>
 #include "xm_blockfft.h"
 
 #include <type_traits>
@@ -1286,6 +1287,96 @@ __global__ void k_phase(const Cx<T>* in, Cx<T>* out, const Cx<T>* __restrict__ p
        i += (long long)gridDim.x * blockDim.x) {
     const int j = (int)(i % n);
     out[i] = in[i] * ph[j];
+  }
+}
+
+// One phase ramp per ROW (xm_phase_apply_rows): out[r, k] = in[r, k] e^{i phi}, phi = rad(p0[r]) + rad(p1[r]) *
+// (c[k] - pivot[r]) / (max c - min c) -- phasing.py:56-73 with the reference's own statements for the angle (no
+// contraction: phi is numpy's to the bit on any axis, uniform or not; at |p1| = 4000 degrees an angle is ~70 rad and
+// one ulp of it is 1.4e-14, so a factorised ramp would sit that far from the reference's table).  A thread owns
+// kPhaseRowsBins consecutive bins: ONE sincos at its middle bin, and for the others e^{i d} of the exact difference d
+// of the two angles (both are doubles of nearly the same size: the subtraction is exact or off by an ulp of d) by a
+// series that is exact to 1e-19 for |d| <= 1/4; a larger step (a short axis under a steep ramp, a gap in a
+// non-uniform axis) takes sincos of its own.  max c - min c is found by every workgroup for itself (n doubles out
+// of the L2) so that the call needs no host pass over a device axis.
+constexpr int kPhaseRowsBins = 8, kPhaseRowsThreads = 256;
+
+__device__ __forceinline__ double phase_rows_angle(double c, double pivot, double x_range, double p0r, double p1r) {
+#pragma clang fp contract(off)
+  return p0r + p1r * ((c - pivot) / x_range);
+}
+
+template <class T>
+__global__ __launch_bounds__(kPhaseRowsThreads) void k_phase_rows(const Cx<T>* in, Cx<T>* out,
+                                                                  const double* __restrict__ coords, long long n_rows, int n,
+                                                                  const double* __restrict__ p0, const double* __restrict__ p1,
+                                                                  const double* __restrict__ pivot,
+                                                                  const int* __restrict__ skip) {
+  constexpr int J = kPhaseRowsBins, NT = kPhaseRowsThreads;
+  __shared__ double s_lo[NT / XM_WAVE], s_hi[NT / XM_WAVE];
+  const int t = (int)threadIdx.x;
+  double lo = DBL_MAX, hi = -DBL_MAX;
+  for (int k = t; k < n; k += NT) {
+    const double c = coords[k];
+    lo = fmin(lo, c);
+    hi = fmax(hi, c);
+  }
+  for (int m = 1; m < XM_WAVE; m <<= 1) {
+    lo = fmin(lo, __shfl_xor(lo, m));
+    hi = fmax(hi, __shfl_xor(hi, m));
+  }
+  if ((t & (XM_WAVE - 1)) == 0) {
+    s_lo[t / XM_WAVE] = lo;
+    s_hi[t / XM_WAVE] = hi;
+  }
+  __syncthreads();
+  for (int w = 0; w < NT / XM_WAVE; ++w) {
+    lo = fmin(lo, s_lo[w]);
+    hi = fmax(hi, s_hi[w]);
+  }
+  const double x_range = hi - lo;
+  const double kRad = 3.14159265358979323846 / 180.0;  // np.radians
+  const long long tiles = (n + J * NT - 1) / (J * NT), total = n_rows * tiles;
+  for (long long i = blockIdx.x; i < total; i += gridDim.x) {
+    const long long row = i / tiles;
+    const int k0 = (int)(i - row * tiles) * (J * NT) + t * J;
+    if (k0 >= n) continue;
+    const int m = n - k0 < J ? n - k0 : J;
+    const Cx<T>* src = in + row * (long long)n + k0;
+    Cx<T>* dst = out + row * (long long)n + k0;
+    Cx<T> v[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (j < m) v[j] = src[j];
+    if (!(skip && skip[row])) {
+      const double p0r = p0[row] * kRad, p1r = p1[row] * kRad, pv = pivot[row];
+      auto angle = [&](int k) { return x_range == 0. ? p0r : phase_rows_angle(coords[k], pv, x_range, p0r, p1r); };
+      const double a_mid = angle(k0 + m / 2);
+      double sm, cm;
+      sincos(a_mid, &sm, &cm);
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        if (j >= m) break;
+        const double d = angle(k0 + j) - a_mid;
+        double er, ei;
+        if (fabs(d) <= 0.25) {
+          const double z = d * d;
+          const double cd = fma(z, fma(z, fma(z, fma(z, fma(z, fma(z, 1.0 / 479001600.0, -1.0 / 3628800.0), 1.0 / 40320.0),
+                                                   -1.0 / 720.0), 1.0 / 24.0), -0.5), 1.0);
+          const double sd = d * fma(z, fma(z, fma(z, fma(z, fma(z, fma(z, 1.0 / 6227020800.0, -1.0 / 39916800.0),
+                                                             1.0 / 362880.0), -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0);
+          er = fma(cm, cd, -(sm * sd));
+          ei = fma(cm, sd, sm * cd);
+        } else {
+          sincos(a_mid + d, &ei, &er);
+        }
+        const double xr = (double)v[j].re, xi = (double)v[j].im;
+        v[j] = mk<T>((T)fma(xr, er, -(xi * ei)), (T)fma(xr, ei, xi * er));
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (j < m) dst[j] = v[j];
   }
 }
 

@@ -308,9 +308,14 @@ struct Drawn {  // the random part of one trial (does not depend on the populati
   bool cross[2];
 };
 
-template <int P, bool FULL>
-__global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
-  __shared__ SearchLds L;
+// One search by one workgroup: the body of both kernels below.  `load(k)` gives bin k of the spectrum as complex128.
+// ROWS (k_search_rows): the record goes to `row_out` in plain device memory, `pivot_given` (not NaN) replaces the
+// arg-max's coordinate as the pivot (with A.target_idx as the target bin), and a row that has no search -- all bins
+// zero, or a sample that is not finite: the ACME score is 0/0 there -- ends before the first evaluation.  Everything
+// the search keeps (MT19937 state, stop word, tables, the optimiser's registers) is set up anew on entry, so the result
+// is a pure function of the row's samples.
+template <int P, bool FULL, bool ROWS, class Load>
+SDEV void search_body(SearchLds& L, const SearchArgs& A, Load load, double pivot_given, xm_search_row* row_out) {
   const int t = (int)threadIdx.x, lane = t & (XM_WAVE - 1), wave = t / XM_WAVE;
   const int n = A.n;
   const bool worker = wave > 0;
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
     for (int j = 0; j <= P; ++j) {
       const int k = k0 + j;
       const bool ok = k < n;
-      const double2 v = ok ? reinterpret_cast<const double2*>(A.slice)[k] : make_double2(0., 0.);
+      const double2 v = ok ? load(k) : make_double2(0., 0.);
       re[j] = v.x;
       im[j] = v.y;
     }
@@ -334,13 +339,15 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
   }
   // ---- first arg-max of |slice| (phasing.py:229 on the winning row; target_idx >= 0: given) ------------------------
   int kwin = A.target_idx;
-  if (kwin < 0) {
+  if (ROWS || kwin < 0) {
     double bv = -1.;
     int bi = 0x7fffffff;
+    bool bad = false;  // ROWS: a sample that is not finite
     if (worker) {
 #pragma unroll
       for (int j = 0; j < P; ++j) {
         const double m2 = re[j] * re[j] + im[j] * im[j];
+        if (ROWS) bad |= k0 + j < n && !(fabs(re[j]) <= DBL_MAX && fabs(im[j]) <= DBL_MAX);
         if (k0 + j < n && m2 > bv) {
           bv = m2;
           bi = k0 + j;
@@ -354,27 +361,47 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
           bi = oi;
         }
       }
+      if (ROWS) bad = __any(bad);
       if (lane == 0) {
         L.amax_v[wave] = bv;
-        L.amax_i[wave] = bi;
+        L.amax_i[wave] = ROWS && bad ? -1 : bi;  // (a bin index is never negative)
       }
     }
     __syncthreads();
     bv = -1.;
     bi = 0x7fffffff;
+    bad = false;
     for (int w = 1; w < kWaves; ++w) {
       const double ov = L.amax_v[w];
       const int oi = L.amax_i[w];
+      if (ROWS && oi < 0) {
+        bad = true;
+        continue;
+      }
       if (ov > bv || (ov == bv && oi < bi)) {
         bv = ov;
         bi = oi;
       }
     }
-    kwin = bi;
+    if constexpr (ROWS) {
+      if (bad || !(bv > 0.)) {  // the same answer in every thread
+        if (t == 0) {
+          const double nan = __longlong_as_double(0x7ff8000000000000ll);
+          row_out->x[0] = row_out->x[1] = row_out->fun = row_out->pg_norm = nan;
+          row_out->nfev = row_out->nit = 0;
+          row_out->target_idx = bad ? -1 : bi;
+          row_out->status = bad ? XM_SEARCH_NOT_FINITE : XM_SEARCH_ALL_ZERO;
+          row_out->needs_polish = 0;
+          row_out->pad_ = 0;
+        }
+        return;
+      }
+    }
+    if (!ROWS || kwin < 0) kwin = bi;
   }
   __syncthreads();
   // u[k] = (c[k] - pivot) / x_range = u0 + k du   (phasing.py:69 on a uniform axis)
-  const double pivot = A.c0 + A.cstep * (double)kwin;
+  const double pivot = ROWS && pivot_given == pivot_given ? pivot_given : A.c0 + A.cstep * (double)kwin;
   const double u0 = (A.c0 - pivot) / A.x_range, du = A.cstep / A.x_range;
   const double kRad = 3.14159265358979323846 / 180.0;  // np.radians
 
@@ -522,8 +549,9 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
 
   // where a search's time goes (wave 0's view, ticks of the 100 MHz wall clock): naming the point, the tables, the
   // overlapped draw, waiting for the workers' sums, taking the score
-  unsigned long long tk[5] = {0, 0, 0, 0, 0}, tk0 = wall_clock64(), tk_start = tk0;
+  unsigned long long tk[5] = {0, 0, 0, 0, 0}, tk0 = ROWS ? 0ull : wall_clock64(), tk_start = tk0;
   auto lap = [&](int which) {
+    if (ROWS) return;  // (the compact record carries no timings)
     const unsigned long long now = wall_clock64();
     tk[which] += now - tk0;
     tk0 = now;
@@ -691,6 +719,28 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
     }
   }
 
+  if (ROWS) {
+    if (t == 0) {
+      double pgn = 0.;
+      for (int i = 0; i < N; ++i) {
+        const double xi = i == 0 ? x0 : x1, lb = i == 0 ? lo0 : lo1, ub = i == 0 ? hi0 : hi1;
+        const double g = (L.vals[1 + i] - L.vals[0]) / L.dx[i];
+        const double pg = g < 0. ? fmax(xi - ub, g) : fmin(xi - lb, g);
+        pgn = fmax(pgn, fabs(pg));
+      }
+      row_out->x[0] = x0;
+      row_out->x[1] = x1;
+      row_out->fun = fun;
+      row_out->pg_norm = pgn;
+      row_out->nfev = nfev;
+      row_out->nit = nit;
+      row_out->target_idx = kwin;
+      row_out->status = status;
+      row_out->needs_polish = pgn <= 0.5e-5 ? 0 : 1;
+      row_out->pad_ = 0;
+    }
+    return;
+  }
   if (t == 0) {
     xm_search_result* o = A.out;
     if (A.n_eval > 0) {
@@ -721,6 +771,57 @@ __global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
       __threadfence_system();
       __hip_atomic_store((unsigned long long*)&o->seq, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+  }
+}
+
+template <int P, bool FULL>
+__global__ __launch_bounds__(kThreads) void k_search(SearchArgs A) {
+  __shared__ SearchLds L;
+  search_body<P, FULL, false>(
+      L, A, [&](int k) { return reinterpret_cast<const double2*>(A.slice)[k]; }, 0., nullptr);
+}
+
+// The same search for every row of in[n_rows, n] (complex64 or complex128, widened to fp64 on load): the grid is the
+// workgroups the stream's CUs hold, rows go round by a grid stride, one record per row.
+struct RowsArgs {
+  const void* in;
+  const unsigned* mt0;
+  xm_search_row* rec;
+  double c0, cstep, x_range, tol, pivot;
+  long long n_rows;
+  int n, p0_only, maxiter, target_idx;
+};
+
+template <int P, bool FULL, class T>
+__global__ __launch_bounds__(kThreads) void k_search_rows(RowsArgs R) {
+  __shared__ SearchLds L;
+  SearchArgs A;
+  A.slice = nullptr;
+  A.mt0 = R.mt0;
+  A.out = nullptr;
+  A.xs = nullptr;
+  A.fs = nullptr;
+  A.c0 = R.c0;
+  A.cstep = R.cstep;
+  A.x_range = R.x_range;
+  A.tol = R.tol;
+  A.seq = 0;
+  A.n = R.n;
+  A.n_eval = 0;
+  A.p0_only = R.p0_only;
+  A.maxiter = R.maxiter;
+  A.target_idx = R.target_idx;
+  using T2 = typename std::conditional<std::is_same<T, float>::value, float2, double2>::type;
+  for (long long row = blockIdx.x; row < R.n_rows; row += gridDim.x) {
+    const T2* src = reinterpret_cast<const T2*>(R.in) + row * (long long)R.n;
+    search_body<P, FULL, true>(
+        L, A,
+        [&](int k) {
+          const T2 v = src[k];
+          return make_double2((double)v.x, (double)v.y);
+        },
+        R.pivot, R.rec + row);
+    __syncthreads();  // the next row's set-up overwrites what a slower wave may still be reading
   }
 }
 
@@ -781,9 +882,78 @@ int launch(const SearchArgs& A, hipStream_t st) {
   return XM_OK;
 }
 
+XmResidency g_rows_residency[7][2][2];  // [P slot][FULL][complex128]
+
+template <int PP, bool FULL, class T>
+int launch_rows_t(const RowsArgs& R, int slot, hipStream_t st) {
+  int resident = 0;
+  const int rc = xm_resident_blocks(g_rows_residency[slot][FULL ? 1 : 0][std::is_same<T, double>::value ? 1 : 0],
+                                    k_search_rows<PP, FULL, T>, kThreads, 0, &resident, st);
+  if (rc) return rc;
+  const long long grid = R.n_rows < (long long)resident ? R.n_rows : (long long)resident;
+  hipLaunchKernelGGL((k_search_rows<PP, FULL, T>), dim3((unsigned)grid), dim3(kThreads), 0, st, R);
+  HIP_TRY(hipGetLastError());
+  return XM_OK;
+}
+
+template <int PP>
+int launch_rows_p(const RowsArgs& R, int slot, int dtype, hipStream_t st) {
+  const bool full = R.n == kWorkers * PP;
+  if (dtype == XM_C64)
+    return full ? launch_rows_t<PP, true, float>(R, slot, st) : launch_rows_t<PP, false, float>(R, slot, st);
+  return full ? launch_rows_t<PP, true, double>(R, slot, st) : launch_rows_t<PP, false, double>(R, slot, st);
+}
+
+int launch_rows(const RowsArgs& R, int dtype, hipStream_t st) {
+  switch (points_per_worker(R.n)) {
+    case 1: return launch_rows_p<1>(R, 0, dtype, st);
+    case 2: return launch_rows_p<2>(R, 1, dtype, st);
+    case 3: return launch_rows_p<3>(R, 2, dtype, st);
+    case 5: return launch_rows_p<5>(R, 3, dtype, st);
+    case 10: return launch_rows_p<10>(R, 4, dtype, st);
+    case 19: return launch_rows_p<19>(R, 5, dtype, st);
+    case 37: return launch_rows_p<37>(R, 6, dtype, st);
+    default:
+      return xm_fail(XM_ERR_UNSUPPORTED_N, "device search: at most " + std::to_string(kWorkers * kMaxP) + " bins");
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int xm_search_rows_supported(int n, int method, double x_range, int dtype) {
+  return (dtype == XM_C64 || dtype == XM_C128) ? xm_search_supported(n, method, x_range) : 0;
+}
+
+int xm_search_rows(const void* in, int64_t n_rows, int n, int dtype, double c0, double cstep, double x_range, int p0_only,
+                   unsigned seed, double tol, int maxiter, double pivot, int target_idx, xm_search_row* records,
+                   void* stream) {
+  if (n_rows < 0 || (n_rows > 0 && (!in || !records)) || n < 2 || maxiter < 1 || !(x_range > 0.0) ||
+      (dtype != XM_C64 && dtype != XM_C128))
+    return xm_fail(XM_ERR_INVALID_ARG, "xm_search_rows: bad argument");
+  const bool given = pivot == pivot;
+  if (given ? (target_idx < 0 || target_idx >= n) : target_idx >= 0)
+    return xm_fail(XM_ERR_INVALID_ARG, "xm_search_rows: a pivot comes with its target index in [0, n), no pivot with -1");
+  if (n_rows == 0) return XM_OK;
+  RowsArgs R;
+  std::memset(&R, 0, sizeof(R));
+  int rc = seed_table(seed, &R.mt0);
+  if (rc) return rc;
+  R.in = in;
+  R.rec = records;
+  R.c0 = c0;
+  R.cstep = cstep;
+  R.x_range = x_range;
+  R.tol = tol;
+  R.pivot = pivot;
+  R.n_rows = n_rows;
+  R.n = n;
+  R.p0_only = p0_only ? 1 : 0;
+  R.maxiter = maxiter;
+  R.target_idx = given ? target_idx : -1;
+  return launch_rows(R, dtype, (hipStream_t)stream);
+}
 
 int xm_search_supported(int n, int method, double x_range) {
   return n >= 2 && method == 0 && points_per_worker(n) > 0 && x_range > 0.0 ? 1 : 0;

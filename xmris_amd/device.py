@@ -693,6 +693,71 @@ def search_eval(slice_c128, axis, xs, target_idx: int = -1, p0_only: bool = Fals
     return fs.cpu().numpy()
 
 
+# ---------------------------------------------------------------------------------------------
+# autophase_each: the same search for every row, and one phase ramp per row
+# ---------------------------------------------------------------------------------------------
+SEARCH_ALL_ZERO, SEARCH_NOT_FINITE = 2, 3  # XM_SEARCH_*: rows without a search
+SEARCH_ROW_DTYPE = np.dtype([("x", "<f8", (2,)), ("fun", "<f8"), ("pg_norm", "<f8"), ("nfev", "<i4"), ("nit", "<i4"),
+                             ("target_idx", "<i4"), ("status", "<i4"), ("needs_polish", "<i4"), ("pad_", "<i4")])
+
+
+def search_rows_supported(n: int, method: str = "acme", x_range: float = 1.0, complex128: bool = False) -> bool:
+    """True when `search_rows` takes rows of this length / objective (ACME, 2 <= n <= 16576, a non-degenerate axis)."""
+    from .autophase_solver import METHODS
+
+    return method in METHODS and bool(_lib.load().xm_search_rows_supported(
+        int(n), METHODS.index(method), float(x_range), _lib.XM_C128 if complex128 else _lib.XM_C64))
+
+
+def search_rows(x2d, axis, p0_only: bool = False, seed: int = 42, tol: float = 0.01, maxiter: int = 1000, pivot=None,
+                target_idx: int = -1):
+    """`xm_search_rows`: phasing.py:276-284's differential evolution (ACME) for EVERY row of ``x2d`` = [n_rows, n]
+    contiguous complex64 / complex128 rows, one workgroup per row.  `axis` = `uniform_axis(coords)`.  `pivot` None:
+    every row's pivot is the coordinate of its first arg-max of |X|; otherwise that pivot for all rows, with
+    `target_idx` the bin nearest to it.  Returns the records as a structured array (`SEARCH_ROW_DTYPE`) on the host."""
+    _require_device(x2d)
+    torch = _torch()
+    if x2d.dim() != 2 or not x2d.is_contiguous():
+        raise ValueError("search_rows expects a contiguous [n_rows, n] tensor")
+    nb, n = x2d.shape
+    rec = torch.empty((nb, SEARCH_ROW_DTYPE.itemsize), dtype=torch.uint8, device=x2d.device)
+    _lib.call("xm_search_rows", x2d.data_ptr(), nb, n, _dtype_code(x2d), float(axis[0]), float(axis[1]), float(axis[2]),
+              int(bool(p0_only)), int(seed), float(tol), int(maxiter), float("nan") if pivot is None else float(pivot),
+              -1 if pivot is None else int(target_idx), rec.data_ptr(), _stream(x2d))
+    return rec.cpu().numpy().view(SEARCH_ROW_DTYPE).reshape(nb)
+
+
+def phase_apply_rows(x, axis: int, coords, p0, p1, pivot, skip=None, out=None):
+    """phasing.py:56-73 with one (p0, p1, pivot) per spectrum (`xm_phase_apply_rows`): `p0` / `p1` (degrees) / `pivot`
+    are shaped like `x` without `axis`; rows where `skip` is set are copied through unchanged.  `out`: `x` itself
+    for an update in place (the axis must then be the last one of a contiguous tensor)."""
+    _require_device(x)
+    torch = _torch()
+    x2, restore = _rows(x, axis)
+    nb, n = x2.shape
+    lead = tuple(x.shape[:axis % x.dim()]) + tuple(x.shape[axis % x.dim() + 1:])
+    c = np.array(coords, dtype=np.float64)
+    if c.size != n:
+        raise ValueError(f"coordinate axis has {c.size} points, data axis has {n}")
+
+    def per_row(v, dtype):
+        v = np.array(np.broadcast_to(np.asarray(v, dtype=dtype), lead))  # (a copy: torch wants writable memory)
+        return torch.from_numpy(v.reshape(nb)).to(x.device)
+
+    cd = torch.from_numpy(c).to(x.device)
+    p0d, p1d, pvd = (per_row(v, np.float64) for v in (p0, p1, pivot))
+    skd = per_row(np.asarray(skip) != 0, np.int32) if skip is not None else None
+    if out is not None:
+        if out is not x or x2.data_ptr() != x.data_ptr():
+            raise ValueError("phase_apply_rows: `out` must be `x` itself, contiguous with `axis` last")
+        y2 = x2
+    else:
+        y2 = torch.empty_like(x2)
+    _lib.call("xm_phase_apply_rows", x2.data_ptr(), y2.data_ptr(), cd.data_ptr(), nb, n, p0d.data_ptr(), p1d.data_ptr(),
+              pvd.data_ptr(), skd.data_ptr() if skd is not None else None, _dtype_code(x), _stream(x))
+    return x if out is not None else restore(y2)
+
+
 class ChipPartition:
     """`xm_stream_create`: one compute stream that owns all CUs but `reserved`, and `n_search` streams that own the
     reserved ones (spread over the eight XCDs), as torch stream objects.  Kept for the life of the process."""

@@ -2,10 +2,10 @@
 from .baseline import baseline_als
 from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
-from .phasing import autophase, phase
+from .phasing import autophase, autophase_each, phase
 
 __all__ = ["baseline_als", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
-           "ifftc", "ifftshift", "autophase", "phase"]
+           "ifftc", "ifftshift", "autophase", "autophase_each", "phase"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled

@@ -139,7 +139,8 @@ def _chain_metadata_untouched(src: LabeledArray, root: LabeledArray, steps) -> b
 def autophase(da, dim: str = DIMS.frequency, method: str = "acme", mode: str = "single",
               peak_width: float = 0.5, target_coord: float | None = None, p0_only: bool = False,
               lb: float = 0.0, temp_time_dim: str = DIMS.time, **kwargs):
-    """Automatic phase correction (reference ``phasing.py:161-290``)."""
+    """Automatic phase correction (reference ``phasing.py:161-290``).  ``mode="all"`` raises as the reference's does;
+    one phase pair per spectrum is `autophase_each`."""
     src = as_labeled(da)
     _check_dims(src, dim, "autophase")
     kwargs.setdefault("disp", False)
@@ -185,3 +186,133 @@ def autophase(da, dim: str = DIMS.frequency, method: str = "acme", mode: str = "
                                   p0_only=p0_only, disp=kwargs.get("disp"), threads=aps.burst_threads(),
                                   polish=aps.default_polish())
     return like_input(_phase_labeled(src, x, dim, p0_opt, p1_opt, pivot), da)  # phasing.py:290
+
+
+MSG_ENGINE = "engine must be 'auto', 'device' or 'host'"
+MSG_ENGINE_DEVICE = ("engine='device' needs method='acme', lb == 0, a uniform coordinate axis and 2 <= n <= 16576 "
+                     "points along the dimension")
+
+
+def _solve_rows_host(rows, work, coords, work_coords, target_coord, index_width, method, p0_only, disp):
+    """The host route of `autophase_each`: the native search (`aps.solve`) for every row of `rows` ([n_rows, n], host)
+    on `work` (the same rows, or their line-broadened copies), as many at a time as the CPU budget has threads, one
+    thread each.  Returns (p0, p1, pivot, skip)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    nb = rows.shape[0]
+    p0, p1, pivot = (np.full(nb, np.nan) for _ in range(3))
+    skip = np.zeros(nb, dtype=bool)
+
+    def one(r):
+        row = rows[r]
+        if not np.all(np.isfinite(row)) or not np.any(row):  # the ACME score is 0/0: no search (see DESIGN.md)
+            return r, None
+        if target_coord is not None:  # phasing.py:233-235
+            tidx, pv = int(np.argmin(np.abs(coords - target_coord))), float(target_coord)
+        else:  # phasing.py:229, 237-238 on this row alone
+            tidx = int(np.argmax(np.abs(row)))
+            pv = float(coords[tidx])
+        a, b, _ = aps.solve(np.asarray(work[r], dtype=np.complex128), work_coords, pv, tidx, index_width, method=method,
+                            p0_only=p0_only, disp=disp, threads=1, polish=aps.default_polish())
+        return r, (a, b, pv)
+
+    workers = max(1, min(aps.burst_threads(), nb))
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for r, res in pool.map(one, range(nb)):
+            if res is None:
+                skip[r] = True
+            else:
+                p0[r], p1[r], pivot[r] = res
+    return p0, p1, pivot, skip
+
+
+def _solve_rows_device(x2, coords, axis, target_coord, index_width, p0_only):
+    """The device route: `xm_search_rows` on the rows where they are; the few rows whose best member does not pass
+    scipy's projected-gradient test come to the host and are polished on the reference's route."""
+    if target_coord is not None:
+        recs = dev.search_rows(x2, axis, p0_only=p0_only, pivot=float(target_coord),
+                               target_idx=int(np.argmin(np.abs(coords - target_coord))))
+    else:
+        recs = dev.search_rows(x2, axis, p0_only=p0_only)
+    skip = recs["status"] >= dev.SEARCH_ALL_ZERO
+    p0, p1 = recs["x"][:, 0].copy(), recs["x"][:, 1].copy()
+    if target_coord is not None:
+        pivot = np.where(skip, np.nan, float(target_coord))
+    else:
+        pivot = np.where(skip, np.nan, coords[np.clip(recs["target_idx"], 0, len(coords) - 1)])
+    for r in np.nonzero(recs["needs_polish"] != 0)[0]:
+        row = np.asarray(to_host(x2[int(r)]), dtype=np.complex128)
+        xr, _, _, _ = aps.polish_reference(row, coords, float(pivot[r]), int(recs["target_idx"][r]), index_width, "acme",
+                                           p0_only, recs["x"][r])
+        p0[r] = xr[0]
+        p1[r] = xr[1] if not p0_only else 0.0
+    return p0, p1, pivot, skip
+
+
+def autophase_each(da, dim: str = DIMS.frequency, method: str = "acme", peak_width: float = 0.5,
+                   target_coord: float | None = None, p0_only: bool = False, lb: float = 0.0,
+                   temp_time_dim: str = DIMS.time, engine: str = "auto", **kwargs):
+    """One (p0, p1) per spectrum: every 1-D spectrum along `dim` is phased as the reference's
+    ``autophase(spectrum, mode="single", ...)`` phases that spectrum alone (its own pivot -- the coordinate of its
+    own |X| maximum, or `target_coord` --, the same bounds, seed, tolerance and polish).  What the reference names
+    ``mode="all"`` and does not implement.
+
+    engine="device": the searches run on the GPU, one workgroup per spectrum (ACME, ``lb == 0``, a uniform axis of at
+    most 16576 points); engine="host": the native host search per spectrum on this process's CPUs (every method,
+    any axis, ``lb > 0``); "auto" takes the device where it applies.  The phase is applied on the GPU either way.
+
+    The result has the input's dims, coords and name like `phase`; attrs gain ``phase_p0`` / ``phase_p1`` /
+    ``phase_pivot`` as float64 arrays shaped like the data without `dim` (0-d for a single spectrum) and
+    ``phase_pivot_coord``.  A spectrum that is all zero or holds a value that is not finite has no search: it passes
+    through unchanged with NaN in the three arrays."""
+    src = as_labeled(da)
+    _check_dims(src, dim, "autophase_each")
+    kwargs.setdefault("disp", False)
+    if method not in aps.METHODS:
+        raise ValueError(MSG_METHOD)
+    if engine not in ("auto", "device", "host"):
+        raise ValueError(MSG_ENGINE)
+    coords = np.asarray(src.coords[dim].values, dtype=np.float64)
+    ax = src.get_axis_num(dim)
+    n = src.shape[ax]
+    lead = tuple(s_ for i, s_ in enumerate(src.shape) if i != ax)
+    axis = dev.uniform_axis(coords)
+    x, _ = device_data(src)
+    on_device = (method == "acme" and not lb > 0 and axis is not None
+                 and dev.search_rows_supported(n, method, axis[2], str(x.dtype).endswith("complex128")))
+    if engine == "device" and not on_device:
+        raise ValueError(MSG_ENGINE_DEVICE)
+    index_width = aps.index_width_of(coords, peak_width)  # phasing.py:245-247
+
+    if on_device and engine != "host":
+        x2, _ = dev._rows(x, ax)
+        p0, p1, pivot, skip = _solve_rows_device(x2, coords, axis, target_coord, index_width, p0_only)
+    else:
+        xm = x.movedim(ax, -1) if hasattr(x, "movedim") else np.moveaxis(x, ax, -1)
+        x2 = xm.reshape(-1, n)
+        rows = to_host(x2)
+        work, work_coords = rows, coords
+        if lb > 0:  # phasing.py:250-253 for every row at once: three launches over [n_rows, n]
+            from .fid import apodize_exp, to_fid, to_spectrum
+
+            each = LabeledArray(promote_for_float64_operand(x2), ("__spectrum__", dim), {dim: Coordinate(dim, coords)})
+            tmp = to_spectrum(apodize_exp(to_fid(each, dim=dim, out_dim=temp_time_dim), dim=temp_time_dim, lb=lb),
+                              dim=temp_time_dim, out_dim=dim)
+            work, work_coords = tmp.values, tmp.coords[dim].values
+        p0, p1, pivot, skip = _solve_rows_host(rows, work, coords, work_coords, target_coord, index_width, method,
+                                               p0_only, kwargs.get("disp"))
+
+    p0, p1, pivot, skip = (v.reshape(lead) for v in (p0, p1, pivot, skip))
+    y = dev.phase_apply_rows(promote_for_float64_operand(x), ax, coords, np.where(skip, 0.0, p0), np.where(skip, 0.0, p1),
+                             np.where(skip, 0.0, pivot), skip=skip)
+    out = src.copy(data=y)
+    out.name = binary_op_name(src, dim)
+    out.attrs = _copy.copy(src.attrs)
+    old = out.attrs.get(ATTRS.phase_pivot_coord)
+    if old is not None and old != dim:  # phasing.py:79-88
+        warnings.warn(msg_phase_units(dim, old, "one per spectrum" if target_coord is None else target_coord))
+    out.attrs[ATTRS.phase_p0] = p0
+    out.attrs[ATTRS.phase_p1] = p1
+    out.attrs[ATTRS.phase_pivot] = pivot
+    out.attrs[ATTRS.phase_pivot_coord] = dim
+    return like_input(out, da)
