@@ -244,6 +244,19 @@ int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n,
                   const double* init, const double* lower, const double* upper, const int32_t* fixed, int max_iter,
                   double ftol, double xtol, double* params, double* amp_sd, double* rss, int32_t* status,
                   int32_t* iters, void* fit_data, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+/* xm_amares_fit_linked: xm_amares_fit with linked prior knowledge.  Three more HOST arrays of 5 n_peaks values (all
+ * NULL: no links): link_to[q] = the root m of parameter q, or -1; then p_q = link_scale[q] p_m + link_offset[q], q
+ * shares m's free column (and m's bounds transform; q's own init / lower / upper / fixed are not read), and a q whose
+ * root is fixed is fixed at the mapped value.  The free parameters P -- n >= P, amp_sd's J^T J -- are the distinct free
+ * columns; amp_sd of a linked amplitude is |link_scale| times its root's.  The root must be the same kind of parameter
+ * (m % 5 == q % 5) of another peak and not itself linked (the caller composes chains); link_scale finite and nonzero,
+ * link_offset finite: otherwise XM_ERR_INVALID_ARG before any HIP call.  xm_amares_fit is this call without links. */
+int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch, int n, double dt, double t0,
+                         int n_peaks, const double* init, const double* lower, const double* upper,
+                         const int32_t* fixed, const int32_t* link_to, const double* link_scale,
+                         const double* link_offset, int max_iter, double ftol, double xtol, double* params,
+                         double* amp_sd, double* rss, int32_t* status, int32_t* iters, void* fit_data, void* workspace,
+                         int64_t workspace_bytes, int dtype, void* stream);
 
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference

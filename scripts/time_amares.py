@@ -7,6 +7,11 @@ fp64 rate from the FLOP count below, and the one-core voxels/s of the CPU oracle
 The kernel time of a separate `rocprofv3 --kernel-trace --stats` run is merged in with --kernel-stats.
 
     python scripts/time_amares.py --out profiles/amares/time_amares.json [--kernel-stats <..._kernel_stats.csv>]
+
+--linked / --nine-unlinked: the 9-line model instead (PCr, Pi, gamma-ATP x 2, alpha-ATP x 2, beta-ATP x 3; multiplet
+amplitudes, shifts (-J, -2J in Hz), linewidths and phases linked to the first line of each multiplet, g fixed: 45
+parameters, 20 free columns), respectively the same nine peaks with only g fixed (36 free columns), on the same seeded
+linked truth (tests/_amares_links.py::multiplet_pk).
 """
 import os
 
@@ -26,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import _amares_links as lk  # noqa: E402
 import _amares_oracle as orc  # noqa: E402
 
 
@@ -62,6 +68,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--oracle-voxels", type=int, default=64)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--linked", action="store_true", help="the 9-line multiplet workload with its links")
+    ap.add_argument("--nine-unlinked", action="store_true", help="the same nine peaks, every line on its own")
     ap.add_argument("--kernel-stats", default=None, help="merge a rocprofv3 kernel_stats.csv into --out and exit")
     a = ap.parse_args()
 
@@ -86,21 +94,44 @@ def main():
 
     mhz, sw, n, nv = 120.0, 10000.0, a.points, a.voxels
     rng = np.random.default_rng(2024)
-    truth = np.zeros((nv, 5, 5))
-    truth[:, :, 0] = np.array(orc.P31_AMP) * rng.uniform(0.6, 1.4, (nv, 5))
-    truth[:, :, 1] = (np.array(orc.P31_PPM) + rng.uniform(-0.15, 0.15, (nv, 5))) * mhz
-    truth[:, :, 2] = np.array(orc.P31_LW) * rng.uniform(0.8, 1.2, (nv, 5)) * np.pi
-    truth[:, :, 3] = rng.uniform(-0.3, 0.3, (nv, 1))
+    nine = a.linked or a.nine_unlinked
+    links = None
+    if nine:
+        init, lo, hi, fixed, links = lk.multiplet_pk(mhz)
+        E, b, roots = lk.expansion(links, 9)
+        truth = np.broadcast_to(init, (nv, 9, 5)).copy()
+        truth[:, :, 0] *= rng.uniform(0.6, 1.4, (nv, 9))
+        truth[:, :, 1] += rng.uniform(-0.15, 0.15, (nv, 9)) * mhz
+        truth[:, :, 2] *= rng.uniform(0.8, 1.2, (nv, 9))
+        truth[:, :, 3] = rng.uniform(-0.3, 0.3, (nv, 1))
+        truth = (truth.reshape(nv, 45)[:, roots] @ E.T + b).reshape(nv, 9, 5)  # the followers obey their links
+        if a.nine_unlinked:  # every line free within +-0.4 ppm, 4 ... 60 Hz, +-180 deg of its own; g still fixed
+            to = links[0] >= 0
+            lo[to[:, 0], 0], hi[to[:, 0], 0] = 0.0, np.inf
+            lo[to[:, 1], 1], hi[to[:, 1], 1] = init[to[:, 1], 1] - 0.4 * mhz, init[to[:, 1], 1] + 0.4 * mhz
+            lo[to[:, 2], 2], hi[to[:, 2], 2] = 4 * np.pi, 60 * np.pi
+            lo[to[:, 3], 3], hi[to[:, 3], 3] = -np.pi, np.pi
+            links = None
+    else:
+        truth = np.zeros((nv, 5, 5))
+        truth[:, :, 0] = np.array(orc.P31_AMP) * rng.uniform(0.6, 1.4, (nv, 5))
+        truth[:, :, 1] = (np.array(orc.P31_PPM) + rng.uniform(-0.15, 0.15, (nv, 5))) * mhz
+        truth[:, :, 2] = np.array(orc.P31_LW) * rng.uniform(0.8, 1.2, (nv, 5)) * np.pi
+        truth[:, :, 3] = rng.uniform(-0.3, 0.3, (nv, 1))
     x = dev.amares_model(torch.from_numpy(truth).to("cuda"), n, 1.0 / sw, 0.0)
     g = torch.Generator(device="cuda").manual_seed(2024)
     x = (x + 0.5 * torch.complex(torch.randn(x.shape, generator=g, device="cuda", dtype=torch.float64),
                                  torch.randn(x.shape, generator=g, device="cuda", dtype=torch.float64)))
     x = x.to(torch.complex64).contiguous()
-    init, lo, hi = orc.p31_pk(mhz)
-    fixed = np.zeros((5, 5), bool)
+    if not nine:
+        init, lo, hi = orc.p31_pk(mhz)
+        fixed = np.zeros((5, 5), bool)
+    n_peaks = init.shape[0]
 
     def run():
-        return dev.amares_fit(x, 1, init, lo, hi, fixed, dt=1.0 / sw, want_fit=False)
+        if links is None:
+            return dev.amares_fit(x, 1, init, lo, hi, fixed, dt=1.0 / sw, want_fit=False)
+        return dev.amares_fit(x, 1, init, lo, hi, fixed, dt=1.0 / sw, want_fit=False, links=links)
 
     for _ in range(a.warmup):
         run()
@@ -117,19 +148,21 @@ def main():
     iters = res.iters.cpu().numpy()
     status = res.status.cpu().numpy()
     amp = res.params.cpu().numpy()[:, :, 0]
-    p_free = 25  # five peaks x (a, f, d, phi, g); g starts on its bound and is held there by its zero slope
-    flop = float(sum(flops_per_voxel(n, 5, p_free, int(i)) for i in iters))
+    # five peaks x (a, f, d, phi, g): g starts on its bound and is held there by its zero slope; nine peaks: g is fixed
+    p_free = res.n_free if nine else 25
+    flop = float(sum(flops_per_voxel(n, n_peaks, p_free, int(i)) for i in iters))
     rec = {
-        "workload": {"voxels": nv, "points": n, "peaks": 5, "free_parameters": p_free, "dtype": "complex64",
-                     "sw_hz": sw, "mhz": mhz},
+        "workload": {"voxels": nv, "points": n, "peaks": n_peaks, "free_parameters": p_free, "dtype": "complex64",
+                     "sw_hz": sw, "mhz": mhz,
+                     "model": "linked multiplets" if a.linked else "nine unlinked" if nine else "five singlets"},
         "fit_seconds": times, "fit_seconds_median": t_med, "voxels_per_s": nv / t_med,
         "iterations_mean": float(iters.mean()), "iterations_max": int(iters.max()),
         "status_counts": {str(s): int((status == s).sum()) for s in (0, 1, 2)},
         "amplitude_rel_err_median": float(np.median(np.abs(amp / truth[:, :, 0] - 1))),
         "flop_per_fit": flop, "fp64_tflops_achieved": flop / t_med / 1e12,
-        "device": torch.cuda.get_device_name(0),
+        "device": torch.cuda.get_device_name(0), "kernel": dev.last_kernel(),
     }
-    if a.oracle_voxels > 0:
+    if a.oracle_voxels > 0 and not nine:
         xh = x[: a.oracle_voxels].cpu().numpy().astype(np.complex128)
         t = np.arange(n) / sw
         t0 = time.perf_counter()

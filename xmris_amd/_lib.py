@@ -56,6 +56,8 @@ SIGNATURES = {
     "xm_amares_workspace_bytes": (_l, [_l, _i, _i]),
     "xm_amares_fit": (_i, [_p, _l, _l, _i, ctypes.c_double, ctypes.c_double, _i, _p, _p, _p, _p, _i, ctypes.c_double,
                            ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
+    "xm_amares_fit_linked": (_i, [_p, _l, _l, _i, ctypes.c_double, ctypes.c_double, _i, _p, _p, _p, _p, _p, _p, _p, _i,
+                                  ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

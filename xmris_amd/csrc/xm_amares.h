@@ -10,6 +10,13 @@
 // and every thread accumulates its own entries of [J | r]^T [J | r] (upper triangle: J^T J and J^T r) over the
 // rounds, always in the same order -- a voxel's result does not depend on the batch it is in or on the workgroup that
 // fits it.  The damped normal equations are solved by a Cholesky factorisation in the LDS.  All arithmetic fp64.
+//
+// Links (k_amares_fit<true>): a linked parameter q follows its root m (the same kind of parameter of another peak) as
+// p_q = sc_q p_m + off_q and shares the root's free column, so P counts columns, not parameters.  The host fills
+// col / bt / lo / hi of a linked q with the root's and composes chains; a follower of a fixed root arrives as a plain
+// fixed parameter.  A staged row is zeroed and the contributions to a column are added in the order peak index
+// ascending, then c ascending -- the order the oracle (tests/_amares_links.py) uses too.  k_amares_fit<false> is the
+// kernel without links: it never reads lk / sc / off and every column has one contribution.
 #pragma once
 #include "xm_common.h"
 
@@ -41,7 +48,10 @@ struct AmaresFitArgs {
   double lo[XM_AM_MAXQ], hi[XM_AM_MAXQ];
   signed char bt[XM_AM_MAXQ];   // XM_AM_* bound type
   signed char col[XM_AM_MAXQ];  // free column of parameter q, -1 when fixed
+  signed char lk[XM_AM_MAXQ];   // 1: q follows the root that owns col[q] (free roots only)
+  double sc[XM_AM_MAXQ], off[XM_AM_MAXQ];  // p_q = sc * p_root + off where lk[q]; 1 and 0 elsewhere
 };
+static_assert(sizeof(AmaresFitArgs) <= 4096, "AmaresFitArgs must fit the 4 KB kernel-argument limit");
 
 // One peak's term at time t: T = a e^{-d (1 - g + g t) t} e^{i (phi + 2 pi f t)}.  One exp and one sincos.
 XM_DEV void am_term(const double* p, double t, double& tr, double& ti) {
@@ -112,13 +122,19 @@ XM_DEV double am_load_re(const AmaresFitArgs& A, long long row, int i, double& i
   return x[0];
 }
 
-// p, s <- physical values / slopes of the internal vector `u` (free parameters; fixed ones keep A.u0)
+// p, s <- physical values / slopes of the internal vector `u` (free parameters; fixed ones keep A.u0).  A linked
+// parameter maps its root's value and slope; an unlinked one takes no part in that arithmetic.
+template <bool LINKED>
 XM_DEV void am_set_params(const AmaresFitArgs& A, const AmLds& L, const double* u) {
   const int t = threadIdx.x;
   if (t < 5 * A.K) {
     const int j = A.col[t];
     double p = A.u0[t], s = 0.0;
     if (j >= 0) am_from_internal(A.bt[t], u[j], A.lo[t], A.hi[t], p, s);
+    if (LINKED && A.lk[t]) {
+      p = A.sc[t] * p + A.off[t];
+      s = A.sc[t] * s;
+    }
     L.p[t] = p;
     L.s[t] = s;
   }
@@ -158,9 +174,30 @@ XM_DEV double am_cost(const AmaresFitArgs& A, const AmLds& L, long long row, dou
   return r;
 }
 
+// factor of parameter q in the physical Jacobian: its link scale (1 for an unlinked parameter, which is exact)
+template <bool LINKED>
+XM_DEV double am_phys(const AmaresFitArgs& A, int q) {
+  return LINKED ? A.sc[q] : 1.0;
+}
+
+// one parameter's pair of entries into column jc of its point's staged rows
+template <bool LINKED>
+XM_DEV void am_put(double* r0, double* r1, int jc, double vr, double vi) {
+  if (LINKED) {
+    r0[jc] += vr;
+    r1[jc] += vi;
+  } else {
+    r0[jc] = vr;
+    r1[jc] = vi;
+  }
+}
+
 // [J | r]^T [J | r] over the row's points into H (upper), hd and g.  `phys`: J with respect to the physical parameters
 // (CRLB), else to the internal ones (J_phys * dp/du).  Thread t owns entries e = t + 256 m of the upper triangle of the
-// (P+1) x (P+1) matrix in row-major order, (P, P) excluded.
+// (P+1) x (P+1) matrix in row-major order, (P, P) excluded.  LINKED: parameters may share a column, so a point's rows
+// are zeroed and accumulated (peak ascending, then c ascending; one thread owns both rows of its point); the factor of
+// a linked parameter is sc * dp/du, and sc alone in the `phys` pass.
+template <bool LINKED>
 XM_DEV void am_normal(const AmaresFitArgs& A, const AmLds& L, long long row, bool phys) {
   const int t = threadIdx.x, P = A.P, lda = A.lda, Q = A.q_pts;
   const int ne_all = (P + 1) * (P + 2) / 2 - 1;
@@ -191,6 +228,8 @@ XM_DEV void am_normal(const AmaresFitArgs& A, const AmLds& L, long long row, boo
       if (i < A.n) {
         const double tt = (double)i * A.dt + A.t0;
         double mr = 0.0, mi = 0.0;
+        if (LINKED)
+          for (int c = 0; c < P; ++c) r0[c] = r1[c] = 0.0;
         for (int k = 0; k < A.K; ++k) {
           const double* p = L.p + 5 * k;
           double tr, ti;
@@ -205,29 +244,24 @@ XM_DEV void am_normal(const AmaresFitArgs& A, const AmLds& L, long long row, boo
             const double e = exp(-p[2] * (1.0 - p[4] + p[4] * tt) * tt);
             double sn, cs;
             sincos(p[3] + 2.0 * M_PI * p[1] * tt, &sn, &cs);
-            const double sc = phys ? 1.0 : L.s[q];
-            r0[jc] = e * cs * sc;
-            r1[jc] = e * sn * sc;
+            const double sc = phys ? am_phys<LINKED>(A, q) : L.s[q];
+            am_put<LINKED>(r0, r1, jc, e * cs * sc, e * sn * sc);
           }
           if ((jc = A.col[q + 1]) >= 0) {
-            const double w = 2.0 * M_PI * tt * (phys ? 1.0 : L.s[q + 1]);
-            r0[jc] = -ti * w;
-            r1[jc] = tr * w;
+            const double w = 2.0 * M_PI * tt * (phys ? am_phys<LINKED>(A, q + 1) : L.s[q + 1]);
+            am_put<LINKED>(r0, r1, jc, -ti * w, tr * w);
           }
           if ((jc = A.col[q + 2]) >= 0) {
-            const double w = -(1.0 - p[4] + p[4] * tt) * tt * (phys ? 1.0 : L.s[q + 2]);
-            r0[jc] = tr * w;
-            r1[jc] = ti * w;
+            const double w = -(1.0 - p[4] + p[4] * tt) * tt * (phys ? am_phys<LINKED>(A, q + 2) : L.s[q + 2]);
+            am_put<LINKED>(r0, r1, jc, tr * w, ti * w);
           }
           if ((jc = A.col[q + 3]) >= 0) {
-            const double w = phys ? 1.0 : L.s[q + 3];
-            r0[jc] = -ti * w;
-            r1[jc] = tr * w;
+            const double w = phys ? am_phys<LINKED>(A, q + 3) : L.s[q + 3];
+            am_put<LINKED>(r0, r1, jc, -ti * w, tr * w);
           }
           if ((jc = A.col[q + 4]) >= 0) {
-            const double w = p[2] * tt * (1.0 - tt) * (phys ? 1.0 : L.s[q + 4]);
-            r0[jc] = tr * w;
-            r1[jc] = ti * w;
+            const double w = p[2] * tt * (1.0 - tt) * (phys ? am_phys<LINKED>(A, q + 4) : L.s[q + 4]);
+            am_put<LINKED>(r0, r1, jc, tr * w, ti * w);
           }
         }
         double xi;
@@ -310,6 +344,7 @@ XM_DEV bool am_solve(const AmaresFitArgs& A, const AmLds& L) {
   return ok;
 }
 
+template <bool LINKED>
 __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
   extern __shared__ double am_sm[];
   const int t = threadIdx.x, P = A.P, K = A.K;
@@ -337,18 +372,18 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
 
     // start: every voxel from the prior knowledge
     for (int q = t; q < 5 * K; q += XM_AM_NT)
-      if (A.col[q] >= 0) L.u[A.col[q]] = A.u0[q];
+      if (A.col[q] >= 0 && !(LINKED && A.lk[q])) L.u[A.col[q]] = A.u0[q];
     if (t < P) L.dsc[t] = 0.0;
     __syncthreads();
-    am_set_params(A, L, L.u);
+    am_set_params<LINKED>(A, L, L.u);
     double F = am_cost(A, L, row, nullptr);
     int status = isfinite(F) ? 1 : 2, it = 0;
     double lam = 1e-3, nu = 2.0;
     bool need_jac = true;
     while (status == 1 && it < A.max_iter) {
       if (need_jac) {
-        am_set_params(A, L, L.u);
-        am_normal(A, L, row, false);
+        am_set_params<LINKED>(A, L, L.u);
+        am_normal<LINKED>(A, L, row, false);
         // Marquardt scaling: the largest squared column norm seen so far (1 for a column that was always zero)
         if (t < P) L.dsc[t] = fmax(L.dsc[t], L.hd[t]);
         __syncthreads();
@@ -374,7 +409,7 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
       const bool xconv = sqrt(dn) <= A.xtol * (sqrt(un) + A.xtol);
       if (t < P) L.ut[t] = L.u[t] + L.dl[t];
       __syncthreads();
-      am_set_params(A, L, L.ut);
+      am_set_params<LINKED>(A, L, L.ut);
       const double Ft = am_cost(A, L, row, nullptr);
       if (isfinite(Ft) && Ft < F) {
         const double rho = fmin(fmax((F - Ft) / pred, 0.0), 1.0);
@@ -394,15 +429,16 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
         if (!isfinite(lam)) break;
       }
     }
-    am_set_params(A, L, L.u);
+    am_set_params<LINKED>(A, L, L.u);
     for (int q = 0; q < 5 * K; ++q)
       if (!isfinite(L.p[q])) status = 2;
     if (!isfinite(F)) status = 2;
 
     double* fit = A.fit ? A.fit + 2 * row * A.n : nullptr;
     if (status != 2) {
-      // CRLB: sigma^2 (J^T J)^{-1} with J over the physical free parameters at the solution; the caller scales
-      am_normal(A, L, row, true);
+      // CRLB: sigma^2 (J^T J)^{-1} with J over the physical free columns at the solution; the caller scales.  A linked
+      // amplitude's variance is sc^2 times its column's.
+      am_normal<LINKED>(A, L, row, true);
       const bool ok = am_cholesky(A, L, 0.0);
       if (t < K) {
         const int j = A.col[5 * t];
@@ -420,7 +456,9 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
             }
           }
         }
-        A.asd[row * K + t] = sqrt(var);
+        double sd = sqrt(var);
+        if (LINKED && A.lk[5 * t]) sd *= fabs(A.sc[5 * t]);
+        A.asd[row * K + t] = sd;
       }
       if (t < 5 * K) A.params[row * 5 * K + t] = L.p[t];
       if (fit) (void)am_cost(A, L, row, fit);

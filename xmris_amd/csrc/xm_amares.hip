@@ -26,7 +26,7 @@ struct AmDeviceGuard {
   }
 };
 
-XmResidency g_am_res;
+XmResidency g_am_res, g_am_res_linked;  // one residency record per kernel instantiation
 
 int am_q_pts(int lda) {  // points per staging round: 128, 64 or 32 so that 2 q lda doubles fit the staging budget
   int q = 128;
@@ -68,10 +68,22 @@ int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n,
                   const double* init, const double* lower, const double* upper, const int32_t* fixed, int max_iter,
                   double ftol, double xtol, double* params, double* amp_sd, double* rss, int32_t* status,
                   int32_t* iters, void* fit_data, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+  return xm_amares_fit_linked(in, in_row_stride, n_batch, n, dt, t0, n_peaks, init, lower, upper, fixed, nullptr, nullptr,
+                              nullptr, max_iter, ftol, xtol, params, amp_sd, rss, status, iters, fit_data, workspace,
+                              workspace_bytes, dtype, stream);
+}
+
+int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch, int n, double dt, double t0,
+                         int n_peaks, const double* init, const double* lower, const double* upper,
+                         const int32_t* fixed, const int32_t* link_to, const double* link_scale,
+                         const double* link_offset, int max_iter, double ftol, double xtol, double* params,
+                         double* amp_sd, double* rss, int32_t* status, int32_t* iters, void* fit_data, void* workspace,
+                         int64_t workspace_bytes, int dtype, void* stream) {
   if (n_peaks < 1 || n_peaks > XM_AM_MAXK) return am_fail("n_peaks must be in 1 ... 16");
   if (n_batch < 0 || n < 1 || in_row_stride < n) return am_fail("needs n_batch >= 0, n >= 1, row stride >= n");
   if (dtype != XM_C64 && dtype != XM_C128) return am_fail("dtype must be XM_C64 or XM_C128");
   if (!init || !lower || !upper || !fixed) return am_fail("null prior-knowledge pointer");
+  if (link_to && (!link_scale || !link_offset)) return am_fail("link_to needs link_scale and link_offset");
   if (n_batch > 0 && (!in || !params || !amp_sd || !rss || !status || !iters || !workspace))
     return am_fail("null pointer");
   if (workspace_bytes < xm_amares_workspace_bytes(n_batch, n, n_peaks))
@@ -93,8 +105,24 @@ int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n,
   A.ftol = ftol;
   A.xtol = xtol;
   // bounds and the internal start values (HOST arrays of 5 n_peaks values: the prior knowledge is shared by the batch)
+  const int Q = 5 * n_peaks;
+  auto linked = [&](int q) { return link_to && link_to[q] >= 0; };
+  for (int q = 0; q < Q; ++q) {
+    A.sc[q] = 1.0;
+    A.off[q] = 0.0;
+    if (!link_to || link_to[q] == -1) continue;
+    const int m = link_to[q];
+    const std::string who = "parameter " + std::to_string(q) + ": ";
+    if (m < -1 || m >= Q) return am_fail(who + "link_to " + std::to_string(m) + " is out of range");
+    if (m == q) return am_fail(who + "linked to itself");
+    if (m % 5 != q % 5) return am_fail(who + "linked to another kind of parameter (" + std::to_string(m) + ")");
+    if (link_to[m] != -1) return am_fail(who + "its root " + std::to_string(m) + " is itself linked (compose chains)");
+    if (!std::isfinite(link_scale[q]) || link_scale[q] == 0.0 || !std::isfinite(link_offset[q]))
+      return am_fail(who + "link_scale must be finite and nonzero, link_offset finite");
+  }
   int P = 0;
-  for (int q = 0; q < 5 * n_peaks; ++q) {
+  for (int q = 0; q < Q; ++q) {
+    if (linked(q)) continue;  // takes everything from its root, below
     const double lo = lower[q], hi = upper[q];
     if (std::isnan(lo) || std::isnan(hi) || lo > hi || !std::isfinite(init[q]))
       return am_fail("parameter " + std::to_string(q) + ": bounds must satisfy lo <= hi, initial value finite");
@@ -124,6 +152,27 @@ int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n,
       A.u0[q] = v;
     }
   }
+  // A linked parameter: the root's column, transform and bounds; its own `lower` / `upper` / `init` / `fixed` are not
+  // read.  A follower of a fixed root is fixed at the mapped value.
+  bool any_link = false;
+  for (int q = 0; q < Q; ++q) {
+    if (!linked(q)) continue;
+    const int m = link_to[q];
+    A.lo[q] = A.lo[m];
+    A.hi[q] = A.hi[m];
+    A.bt[q] = A.bt[m];
+    A.col[q] = A.col[m];
+    if (A.col[m] < 0) {
+      A.u0[q] = link_scale[q] * A.u0[m] + link_offset[q];
+      if (!std::isfinite(A.u0[q])) return am_fail("parameter " + std::to_string(q) + ": a fixed value must be finite");
+      continue;
+    }
+    A.u0[q] = A.u0[m];
+    A.lk[q] = 1;
+    A.sc[q] = link_scale[q];
+    A.off[q] = link_offset[q];
+    any_link = true;
+  }
   if (P < 1) return am_fail("every parameter is fixed");
   if (n < P) return am_fail("n (" + std::to_string(n) + ") smaller than the free parameters (" + std::to_string(P) + ")");
   if (n_batch == 0) return XM_OK;
@@ -144,11 +193,15 @@ int xm_amares_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n,
   HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   const size_t lds = am_lds_bytes(P, A.lda, A.q_pts);
   int resident = 0;
-  const int rc = xm_resident_blocks(g_am_res, k_amares_fit, XM_AM_NT, lds, &resident, st);
+  const int rc = any_link ? xm_resident_blocks(g_am_res_linked, k_amares_fit<true>, XM_AM_NT, lds, &resident, st)
+                          : xm_resident_blocks(g_am_res, k_amares_fit<false>, XM_AM_NT, lds, &resident, st);
   if (rc) return rc;
   const long long blocks = n_batch < resident ? n_batch : resident;
-  xm_note_kernel("k_amares_fit", nullptr, nullptr, P, -1);
-  hipLaunchKernelGGL(k_amares_fit, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
+  xm_note_kernel("k_amares_fit", nullptr, any_link ? "true" : "false", P, -1);  // <LINKED, free columns>
+  if (any_link)
+    hipLaunchKernelGGL(k_amares_fit<true>, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
+  else
+    hipLaunchKernelGGL(k_amares_fit<false>, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
   HIP_TRY(hipGetLastError());
   return XM_OK;
 }

@@ -341,10 +341,13 @@ class AmaresFit:
 
 
 def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, max_iter: int = 200,
-               ftol: float = 1e-10, xtol: float = 1e-10, want_fit: bool = True) -> AmaresFit:
+               ftol: float = 1e-10, xtol: float = 1e-10, want_fit: bool = True, links=None) -> AmaresFit:
     """One Levenberg-Marquardt AMARES fit per FID along `axis` of the complex64 / complex128 device tensor `x`, all
-    voxels in one launch (xm_amares_fit).  init / lo / hi / fixed: [K, 5] prior knowledge in fitting units (a, f [Hz],
-    d [1/s], phi [rad], g), shared by every voxel."""
+    voxels in one launch (xm_amares_fit_linked).  init / lo / hi / fixed: [K, 5] prior knowledge in fitting units (a,
+    f [Hz], d [1/s], phi [rad], g), shared by every voxel.  links: None, or (link_to, link_scale, link_offset), each
+    [K, 5]: parameter q = 5 k + c follows its root link_to[k, c] (a parameter index, -1: not linked) as
+    scale * p_root + offset, in fitting units.  `n_free` of the result counts the free columns of the Jacobian: a
+    group of linked parameters is one."""
     torch = _torch()
     _require_device(x)
     code = _dtype_code(x)
@@ -353,6 +356,14 @@ def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, ma
     k = init.shape[0]
     if not (lo.shape == hi.shape == fixed.shape == init.shape):
         raise ValueError("init, lo, hi and fixed must all be [n_peaks, 5]")
+    if links is None:
+        link_to = np.full((k, 5), -1, dtype=np.int32)
+        link_sc, link_off = np.ones((k, 5)), np.zeros((k, 5))
+    else:
+        link_to = np.ascontiguousarray(np.asarray(links[0]).reshape(-1, 5).astype(np.int32))
+        link_sc, link_off = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1, 5)) for v in links[1:])
+        if not (link_to.shape == link_sc.shape == link_off.shape == init.shape):
+            raise ValueError("links must be three [n_peaks, 5] arrays")
     axis = axis % x.dim()
     x2, restore = _rows(x, axis)
     nb, n = x2.shape
@@ -367,11 +378,11 @@ def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, ma
     need = int(_lib.load().xm_amares_workspace_bytes(nb, n, k))
     work = torch.zeros(max(need, 8), dtype=torch.uint8, device=dev_)
     ptr = lambda a: a.ctypes.data  # noqa: E731  (host prior-knowledge arrays)
-    _lib.call("xm_amares_fit", x2.data_ptr(), n, nb, n, float(dt), float(t0), k, ptr(init), ptr(lo), ptr(hi), ptr(fixed),
-              int(max_iter), float(ftol), float(xtol), params.data_ptr(), asd.data_ptr(), rss.data_ptr(),
-              status.data_ptr(), iters.data_ptr(), fit.data_ptr() if fit is not None else None, work.data_ptr(), need,
-              code, _stream(x))
-    n_free = int(np.count_nonzero(~(fixed.astype(bool) | (lo == hi))))
+    _lib.call("xm_amares_fit_linked", x2.data_ptr(), n, nb, n, float(dt), float(t0), k, ptr(init), ptr(lo), ptr(hi),
+              ptr(fixed), ptr(link_to), ptr(link_sc), ptr(link_off), int(max_iter), float(ftol), float(xtol),
+              params.data_ptr(), asd.data_ptr(), rss.data_ptr(), status.data_ptr(), iters.data_ptr(),
+              fit.data_ptr() if fit is not None else None, work.data_ptr(), need, code, _stream(x))
+    n_free = int(np.count_nonzero(~(fixed.astype(bool) | (lo == hi)) & (link_to < 0)))
     return AmaresFit(params=params.reshape(lead + (k, 5)), amp_sd=asd.reshape(lead + (k,)), rss=rss.reshape(lead),
                      status=status.reshape(lead), iters=iters.reshape(lead),
                      fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)

@@ -24,7 +24,9 @@ def fit_amares(da, prior_knowledge_file, dim: str = "time", mhz: float | None = 
                num_workers: int = 4, init_fid=None, verbose: bool = False):
     """Fit every FID along `dim` with the prior knowledge of `prior_knowledge_file` (CSV).  Returns a LabeledDataset
     (an ``xarray.Dataset`` for DataArray input) with raw_data, fit_data, residuals (the input's dims) and amplitude,
-    chem_shift [ppm], linewidth [Hz], phase [deg], crlb [%], snr (other dims..., "Metabolite").
+    chem_shift [ppm], linewidth [Hz], phase [deg], crlb [%], snr (other dims..., "Metabolite").  Linked prior knowledge
+    (fitting/prior_knowledge.py) needs no keyword: every CSV column stays one "Metabolite" entry, and attrs
+    ["n_free_parameters"] counts the free columns of the fit (a group of linked parameters is one).
     `initialize_with_lm`, `num_workers` and `init_fid` are accepted for compatibility and do not change the result:
     every voxel starts from the prior knowledge's initial values."""
     src = as_labeled(da)
@@ -58,7 +60,8 @@ def fit_amares(da, prior_knowledge_file, dim: str = "time", mhz: float | None = 
     if not x.is_complex():
         x = x.to(torch.complex128 if x.dtype == torch.float64 else torch.complex64)
     x = x.to("cuda")
-    res = dev.amares_fit(x, axis, init, lo, hi, pk.fixed, dt=1.0 / float(sw), t0=float(deadtime))
+    res = dev.amares_fit(x, axis, init, lo, hi, pk.fixed, dt=1.0 / float(sw), t0=float(deadtime),
+                         links=pk.fitting_links(mhz))
 
     params = res.params.cpu().numpy()
     failed = res.status.cpu().numpy() == 2
@@ -95,6 +98,6 @@ def fit_amares(da, prior_knowledge_file, dim: str = "time", mhz: float | None = 
 
     attrs = _copy.copy(src.attrs)
     attrs.update({"fit_method": method, "prior_knowledge_file": str(prior_knowledge_file),
-                  "amares_version": f"xmris_amd {__version__}"})
+                  "amares_version": f"xmris_amd {__version__}", "n_free_parameters": res.n_free})
     ds = LabeledDataset(data_vars, attrs)
     return ds.to_xarray() if is_xarray(da) else ds
