@@ -258,6 +258,29 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
                          double* amp_sd, double* rss, int32_t* status, int32_t* iters, void* fit_data, void* workspace,
                          int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- coil combination (this backend's own definition, the reference has none).
+ * The data are viewed as (n_outer, C, n_inner, N), C-contiguous: voxel (a, b) holds the C x N matrix X of its FIDs, its
+ * coils n_inner N elements apart.  `ref_or_null`: the reference R, (n_outer, C, n_inner, N_R) of the same dtype, or NULL
+ * (R = X, N_R must equal N).  `linv_or_null`: L^{-1} of the noise covariance Psi = L L^H, C x C complex128 row-major on
+ * the device, or NULL for the identity.  Per voxel: G = L^{-1} (R R^H) L^{-H}; u = the unit eigenvector of G's largest
+ * eigenvalue (XM_COIL_SVD; XM_COIL_SVD_FMA, not a user method: the same with the Gram matrix on plain FMAs at every C, the
+ * form the tests and the timing script hold the matrix-core form against) or L^{-1} mean(R[:, :n_points]) normalised (XM_COIL_FIRST_POINT); w = L^{-H} u turned
+ * so that w^H R[:, 0] >= 0; y = w^H X.  Outputs (device): y (n_outer, n_inner, N) of the input's dtype, w (n_outer,
+ * n_inner, C) complex128, quality = u^H G u / trace(G), status: 0 combined; 1 nothing to go by (R all zero, or a zero
+ * mean for first_point): y, w, quality zero; 2 a non-finite sample in R or X, or finite
+ * samples so large that R R^H or its squared norm overflows fp64: y, w zero, quality NaN; 3 the Jacobi
+ * sweep cap was reached (the result is what it had).  All arithmetic fp64.  `workspace`: XM_COIL_WORKSPACE_BYTES of
+ * device memory, zero on entry to the first call and left zero by every call.  1 <= C <= 64, N >= 1, N_R >= 1,
+ * 1 <= n_points <= N_R, a known method and non-NULL x / y / w / quality / status / workspace: otherwise
+ * XM_ERR_INVALID_ARG before any HIP call. */
+#define XM_COIL_SVD 0
+#define XM_COIL_FIRST_POINT 1
+#define XM_COIL_SVD_FMA 2
+#define XM_COIL_WORKSPACE_BYTES 256
+int xm_coil_combine(const void* x, const void* ref_or_null, void* y, void* w, double* quality, int32_t* status,
+                    int64_t n_outer, int C, int64_t n_inner, int N, int N_R, const void* linv_or_null, int method,
+                    int n_points, int is_complex128, void* workspace, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

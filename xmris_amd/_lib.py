@@ -20,6 +20,11 @@ XM_FFT_SHIFT_OUT = 8
 XM_AMAX_VALUE_ONLY = 16
 XM_AMAX_GLOBAL_KEY = 32
 
+XM_COIL_SVD = 0
+XM_COIL_FIRST_POINT = 1
+XM_COIL_SVD_FMA = 2
+XM_COIL_WORKSPACE_BYTES = 256
+
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
 XM_ERR_HIP = -3
@@ -58,6 +63,7 @@ SIGNATURES = {
                            ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "xm_amares_fit_linked": (_i, [_p, _l, _l, _i, ctypes.c_double, ctypes.c_double, _i, _p, _p, _p, _p, _p, _p, _p, _i,
                                   ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
+    "xm_coil_combine": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _p, _i, _i, _i, _p, _p]),
     "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

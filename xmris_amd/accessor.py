@@ -57,6 +57,14 @@ class XmrisProcessingMixin:
 
         return baseline_als(self._obj, dim=dim, lam=lam, p=p, n_iter=n_iter)
 
+    def combine_coils(self, dim: str = DIMS.coil, time_dim: str = DIMS.time, method: str = "svd", reference=None,
+                      noise_cov=None, n_points: int = 1, return_weights: bool = False):
+        """Per-voxel coil combination on the GPU (an addition of this backend)."""
+        from .processing.coils import combine_coils
+
+        return combine_coils(self._obj, dim=dim, time_dim=time_dim, method=method, reference=reference,
+                             noise_cov=noise_cov, n_points=n_points, return_weights=return_weights)
+
 
 class XmrisPhasingMixin:
     def phase(self, dim: str = DIMS.frequency, p0: float = 0.0, p1: float = 0.0, pivot: float = None):

@@ -53,6 +53,8 @@ class _Attrs(_Vocabulary):
     baseline_lam = XmrisTerm("baseline_lam", "Smoothness penalty of the AsLS baseline.")
     baseline_p = XmrisTerm("baseline_p", "Asymmetry parameter of the AsLS baseline.")
     baseline_iter = XmrisTerm("baseline_iter", "Number of AsLS re-weighting iterations.")
+    coil_combine_method = XmrisTerm("coil_combine_method", "How the receive coils were combined: 'svd' or 'first_point'.")
+    coil_combine_dim = XmrisTerm("coil_combine_dim", "Name of the coil dimension that was combined away.")
 
 
 class _Dims(_Vocabulary):

@@ -8,24 +8,6 @@
 static int am_fail(const std::string& msg) { return xm_fail(XM_ERR_INVALID_ARG, "amares: " + msg); }
 
 namespace {
-// the device that owns `ptr` is current for the duration of a call (see the conventions in xmris_hip.h)
-struct AmDeviceGuard {
-  int prev = -1;
-  explicit AmDeviceGuard(const void* ptr) {
-    hipPointerAttribute_t at;
-    if (!ptr || hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    int cur = 0;
-    if (at.type != hipMemoryTypeDevice || hipGetDevice(&cur) != hipSuccess) return;
-    if (cur != at.device && hipSetDevice(at.device) == hipSuccess) prev = cur;
-  }
-  ~AmDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 XmResidency g_am_res, g_am_res_linked;  // one residency record per kernel instantiation
 
 int am_q_pts(int lda) {  // points per staging round: 128, 64 or 32 so that 2 q lda doubles fit the staging budget
@@ -54,7 +36,7 @@ int xm_amares_model(const double* params, int64_t n_batch, int n_peaks, int n, d
   if (n_batch > 0 && (!params || !out)) return am_fail("model: null pointer");
   if (!std::isfinite(dt) || !std::isfinite(t0)) return am_fail("model: dt and t0 must be finite");
   if (n_batch == 0) return XM_OK;
-  AmDeviceGuard guard(out);
+  DeviceGuard guard(out);
   const long long total = (long long)n_batch * n;
   long long blocks = (total + 255) / 256;
   if (blocks > 65536) blocks = 65536;
@@ -188,7 +170,7 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
   A.fit = (double*)fit_data;
   A.counter = (unsigned*)workspace;
 
-  AmDeviceGuard guard(in);
+  DeviceGuard guard(in);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   const size_t lds = am_lds_bytes(P, A.lda, A.q_pts);

@@ -202,28 +202,6 @@ int xm_ramp_table_async(void* table, int n, double phase0, double dphase, int dt
   return XM_OK;
 }
 
-// The library keys its table cache, occupancy caches and scratch on the CURRENT device; the caller's buffers decide
-// which device that has to be.  Entry points that launch kernels make the device of their (device-memory) input
-// current for the duration of the call.
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(const void* dev_ptr) {
-    if (!dev_ptr) return;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dev_ptr) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    if (at.type != hipMemoryTypeDevice) return;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return;
-    if (cur != at.device && hipSetDevice(at.device) == hipSuccess) prev = cur;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 static int grid_for(long long total, int block) {
   long long g = (total + block - 1) / block;
   const long long cap = 256LL * 16;  // 256 CUs x 16 workgroups, grid-stride the rest

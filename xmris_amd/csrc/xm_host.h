@@ -23,6 +23,28 @@ int xm_fail(int code, const std::string& msg);
     }                                                                                \
   } while (0)
 
+// The library keys its table cache, occupancy caches and scratch on the CURRENT device; the caller's buffers decide
+// which device that has to be.  Entry points that launch kernels make the device of their (device-memory) input
+// current for the duration of the call.
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(const void* dev_ptr) {
+    if (!dev_ptr) return;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, dev_ptr) != hipSuccess) {
+      (void)hipGetLastError();
+      return;
+    }
+    if (at.type != hipMemoryTypeDevice) return;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess) return;
+    if (cur != at.device && hipSetDevice(at.device) == hipSuccess) prev = cur;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
 enum XmTableKind { TK_TWIDDLE = 0, TK_HALF = 1, TK_CHIRP = 2, TK_CHIRP_FFT = 3, TK_BIG_WN = 4 };
 
 // Cached device table (kind, n, m, dtype, current device).  `gen` fills re/im in fp64 when the table

@@ -388,6 +388,79 @@ def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, ma
                      fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)
 
 
+class CoilCombine:
+    """Raw outputs of ``coil_combine`` with the axes of the input other than coil and time in front, in the input's
+    order: y [..., N] (the input's dtype), weights [..., C] complex128, quality [...] fp64, status [...] int32
+    (0 combined, 1 nothing to go by, 2 non-finite sample, 3 Jacobi sweep cap)."""
+
+    __slots__ = ("y", "weights", "quality", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+COIL_METHODS = {"svd": _lib.XM_COIL_SVD, "first_point": _lib.XM_COIL_FIRST_POINT, "svd_fma": _lib.XM_COIL_SVD_FMA}
+
+
+def coil_combine(x, coil_axis: int, time_axis: int, method: str = "svd", reference=None, linv=None,
+                 n_points: int = 1, workspace=None) -> CoilCombine:
+    """Per-voxel coil combination of the complex64 / complex128 device tensor `x` in one launch (xm_coil_combine,
+    DESIGN.md section 10).  `reference`: a tensor with x's axes and sizes except along `time_axis`; the weights then
+    come from it alone.  `linv`: L^{-1} of the noise covariance L L^H, [C, C] (host or device), or None for the
+    identity.  With time as the last axis of a contiguous tensor the kernel addresses the coil axis where it is;
+    any other layout costs one contiguous copy (time moved last).  "svd_fma" is "svd" with the Gram matrix on plain
+    FMAs (verification).  `workspace`: a zeroed uint8 tensor of XM_COIL_WORKSPACE_BYTES to reuse between calls."""
+    torch = _torch()
+    _require_device(x)
+    if method not in COIL_METHODS:
+        raise ValueError(f"method must be one of {tuple(COIL_METHODS)}, got {method!r}")
+    nd = x.dim()
+    coil_axis, time_axis = coil_axis % nd, time_axis % nd
+    if coil_axis == time_axis:
+        raise ValueError("coil_axis and time_axis must differ")
+
+    def rows(a):  # time last, C-contiguous
+        if time_axis != nd - 1:
+            a = torch.movedim(a, time_axis, -1)
+        return a if a.is_contiguous() else a.contiguous()
+
+    ca = coil_axis if coil_axis < time_axis else coil_axis - 1  # where the coil axis is once time is last
+    xr = rows(x)
+    code = _dtype_code(xr)
+    shape = tuple(xr.shape)
+    c, n = shape[ca], shape[-1]
+    n_outer = int(np.prod(shape[:ca], dtype=np.int64))
+    n_inner = int(np.prod(shape[ca + 1:-1], dtype=np.int64))
+    lead = shape[:ca] + shape[ca + 1:-1]
+    n_ref, rr = n, None
+    if reference is not None:
+        _require_device(reference)
+        if reference.dim() != nd or reference.dtype != x.dtype:
+            raise ValueError("reference must have x's dtype and number of axes")
+        rr = rows(reference)
+        if tuple(rr.shape[:-1]) != shape[:-1]:
+            raise ValueError(f"reference shape {tuple(reference.shape)} does not match x {tuple(x.shape)} off the time axis")
+        n_ref = rr.shape[-1]
+    li = None
+    if linv is not None:
+        li = torch.as_tensor(np.ascontiguousarray(linv, dtype=np.complex128) if not hasattr(linv, "detach") else linv)
+        li = li.to(x.device, torch.complex128).contiguous()
+        if tuple(li.shape) != (c, c):
+            raise ValueError(f"linv must be [{c}, {c}], got {tuple(li.shape)}")
+    dev_ = x.device
+    y = torch.empty(lead + (n,), dtype=x.dtype, device=dev_)
+    w = torch.empty(lead + (c,), dtype=torch.complex128, device=dev_)
+    quality = torch.empty(lead, dtype=torch.float64, device=dev_)
+    status = torch.empty(lead, dtype=torch.int32, device=dev_)
+    work = workspace if workspace is not None else torch.zeros(_lib.XM_COIL_WORKSPACE_BYTES, dtype=torch.uint8, device=dev_)
+    _lib.call("xm_coil_combine", xr.data_ptr(), rr.data_ptr() if rr is not None else None, y.data_ptr(), w.data_ptr(),
+              quality.data_ptr(), status.data_ptr(), n_outer, c, n_inner, n, n_ref,
+              li.data_ptr() if li is not None else None, COIL_METHODS[method], int(n_points),
+              int(code == _lib.XM_C128), work.data_ptr(), _stream(x))
+    return CoilCombine(y=y, weights=w, quality=quality, status=status)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
