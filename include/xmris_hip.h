@@ -281,6 +281,35 @@ int xm_coil_combine(const void* x, const void* ref_or_null, void* y, void* w, do
                     int64_t n_outer, int C, int64_t n_inner, int N, int N_R, const void* linv_or_null, int method,
                     int n_points, int is_complex128, void* workspace, void* stream);
 
+/* ---- alignment of repeated transients (this backend's own definition, the reference has none).
+ * The data are viewed as (n_outer, A, n_inner, N), C-contiguous, time last: transient (o, a, i) starts at
+ * ((o A + a) n_inner + i) N.  `r`: the references, N_r points each, the one of voxel v = o n_inner + i at
+ * v r_voxel_stride elements (0: one row shared by all voxels), the data's dtype.  With tau_t = t0 + t dt and
+ * z_t = r_t conj(x_t), t < L: C(f) = sum_t z_t e^{-2 pi i f tau_t}; g* = the arg-max of |C|^2 on the grid g delta,
+ * delta = 1 / (4 L dt), |g| <= G = floor(max_shift / delta) (G = 0 when L < 2), a tie going to the smallest |g|, then to
+ * the negative g; f* = the zero of d|C|^2 / df in [(g* - 1) delta, (g* + 1) delta] within +-max_shift (safeguarded
+ * Newton, at most 40 steps, until a step <= 2^-40 delta); phi* = arg C(f*); y_t = x_t e^{i (2 pi f* tau_t + phi*)},
+ * t < N.  Outputs (device), per transient in the layout (n_outer, A, n_inner): shift = f* (Hz), phase = phi* (rad),
+ * quality = |C(f*)| / (||r|| ||x||), status: 0 aligned; 1 |g*| = G and |C|^2 still rises at that end of the window:
+ * f* = +-max_shift, unrefined; 2 a non-finite sample among the L points of x or r, or a sum that overflows: y zero,
+ * shift, phase, quality NaN; 3 C zero on the whole grid: y = x, shift, phase, quality 0; 4 the step cap was reached
+ * (the result is what the iteration had).  `y`: as x, the input's dtype.  Averaging form (`mean_or_null` given): per
+ * voxel the mean (n_outer, n_inner, N) of the y with status != 2 and quality >= min_quality, summed in fp64 in
+ * ascending a and divided by their number, which goes to `n_averaged_or_null` (int32 per voxel; zero: a zero mean);
+ * `y` may then be NULL.  `dtype`: XM_C64 / XM_C128; XM_ALIGN_SKIP_* on top of it leave a stage out (timing only).
+ * `workspace`: xm_align_workspace_bytes(...) of device memory, zero on entry to the first call and left zero by
+ * every call.  XM_ERR_INVALID_ARG before any HIP call for: a NULL pointer other than the optional ones, L < 1,
+ * L > min(N, N_r), L > 8192, 2 G + 1 > 1025, dt <= 0, max_shift < 0, a stride between 1 and N_r - 1, an unknown dtype. */
+#define XM_ALIGN_WORKSPACE_BYTES 256
+#define XM_ALIGN_SKIP_COARSE 0x100
+#define XM_ALIGN_SKIP_REFINE 0x200
+#define XM_ALIGN_SKIP_APPLY 0x400
+int64_t xm_align_workspace_bytes(int64_t n_outer, int A, int64_t n_inner, int N);
+int xm_align_rows(const void* x, const void* r, int64_t r_voxel_stride, void* y, void* mean_or_null, double* shift,
+                  double* phase, double* quality, int32_t* status, int32_t* n_averaged_or_null, int64_t n_outer, int A,
+                  int64_t n_inner, int N, int N_r, int L, double dt, double t0, double max_shift, double min_quality,
+                  int dtype, void* workspace, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -65,6 +65,16 @@ class XmrisProcessingMixin:
         return combine_coils(self._obj, dim=dim, time_dim=time_dim, method=method, reference=reference,
                              noise_cov=noise_cov, n_points=n_points, return_weights=return_weights)
 
+    def align_averages(self, dim: str = DIMS.average, time_dim: str = DIMS.time, reference="mean", max_shift: float = 20.0,
+                       t_max: float = None, n_points: int = None, passes: int = 1, average: bool = False,
+                       min_quality: float = 0.0, return_shifts: bool = False):
+        """Per-transient frequency and phase correction on the GPU (an addition of this backend)."""
+        from .processing.align import align_averages
+
+        return align_averages(self._obj, dim=dim, time_dim=time_dim, reference=reference, max_shift=max_shift,
+                              t_max=t_max, n_points=n_points, passes=passes, average=average, min_quality=min_quality,
+                              return_shifts=return_shifts)
+
 
 class XmrisPhasingMixin:
     def phase(self, dim: str = DIMS.frequency, p0: float = 0.0, p1: float = 0.0, pivot: float = None):

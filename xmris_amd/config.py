@@ -55,6 +55,9 @@ class _Attrs(_Vocabulary):
     baseline_iter = XmrisTerm("baseline_iter", "Number of AsLS re-weighting iterations.")
     coil_combine_method = XmrisTerm("coil_combine_method", "How the receive coils were combined: 'svd' or 'first_point'.")
     coil_combine_dim = XmrisTerm("coil_combine_dim", "Name of the coil dimension that was combined away.")
+    align_dim = XmrisTerm("align_dim", "Name of the dimension whose transients were frequency- and phase-aligned.")
+    align_reference = XmrisTerm("align_reference", "What the transients were aligned to: 'mean', 'first', an index or 'array'.")
+    align_max_shift = XmrisTerm("align_max_shift", "Largest frequency shift the alignment searched.", "Hz")
 
 
 class _Dims(_Vocabulary):

@@ -461,6 +461,95 @@ def coil_combine(x, coil_axis: int, time_axis: int, method: str = "svd", referen
     return CoilCombine(y=y, weights=w, quality=quality, status=status)
 
 
+class AlignRows:
+    """Raw outputs of ``align_rows``, the input's axes other than time in front and in the input's order: y like x
+    (time last) or None, shift (Hz), phase (rad), quality fp64 and status int32 per transient (0 aligned, 1 window edge,
+    2 non-finite, 3 nothing to go by, 4 step cap); averaging form: mean [voxels..., N] and n_averaged int32 per voxel."""
+
+    __slots__ = ("y", "mean", "shift", "phase", "quality", "status", "n_averaged")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+ALIGN_MAX_POINTS = 8192
+ALIGN_MAX_GRID = 1025
+ALIGN_SKIP = {"coarse": _lib.XM_ALIGN_SKIP_COARSE, "refine": _lib.XM_ALIGN_SKIP_REFINE, "apply": _lib.XM_ALIGN_SKIP_APPLY}
+
+
+def align_grid(n_points: int, dt: float, max_shift: float):
+    """(delta, G) of the coarse grid of xm_align_rows: delta = 1 / (4 L dt), G = floor(max_shift / delta), and G = 0
+    for a single point."""
+    delta = 1.0 / (4.0 * n_points * dt)
+    return delta, (int(np.floor(max_shift / delta)) if n_points >= 2 else 0)
+
+
+def align_rows(x, average_axis: int, time_axis: int, reference, n_points: int, dt: float, t0: float = 0.0,
+               max_shift: float = 20.0, average: bool = False, min_quality: float = 0.0, want_y: bool = True,
+               workspace=None, _skip=()) -> AlignRows:
+    """Frequency-and-phase alignment of every transient of the complex64 / complex128 device tensor `x` to its voxel's
+    reference in one launch (xm_align_rows).  `reference`: a tensor shaped like x without
+    `average_axis` (its time axis any length >= n_points), or 1-D along time, shared by all voxels.  `n_points`: the
+    leading points L the fit uses.  With time as the last axis of a contiguous tensor the kernel addresses the average
+    axis where it is; any other layout costs one contiguous copy (time moved last).  `average`: also the per-voxel mean
+    of the aligned transients with status != 2 and quality >= min_quality (`want_y=False`: only that).  `_skip`
+    (tests and timing only): stages to leave out, of "coarse", "refine", "apply"."""
+    torch = _torch()
+    _require_device(x)
+    _require_device(reference)
+    nd = x.dim()
+    average_axis, time_axis = average_axis % nd, time_axis % nd
+    if average_axis == time_axis:
+        raise ValueError("average_axis and time_axis must differ")
+    if reference.dtype != x.dtype:
+        raise ValueError("reference must have x's dtype")
+
+    def rows(a, axis):  # time last, C-contiguous
+        if axis != a.dim() - 1:
+            a = torch.movedim(a, axis, -1)
+        return a if a.is_contiguous() else a.contiguous()
+
+    aa = average_axis if average_axis < time_axis else average_axis - 1  # where the average axis is once time is last
+    xr = rows(x, time_axis)
+    code = _dtype_code(xr)
+    shape = tuple(xr.shape)
+    a_, n = shape[aa], shape[-1]
+    n_outer = int(np.prod(shape[:aa], dtype=np.int64))
+    n_inner = int(np.prod(shape[aa + 1:-1], dtype=np.int64))
+    vox = shape[:aa] + shape[aa + 1:-1]
+    if reference.dim() == 1:
+        rr, stride = rows(reference, 0), 0
+    else:
+        if reference.dim() != nd - 1:
+            raise ValueError("reference must be 1-D along time or have x's axes without the average axis")
+        rr = rows(reference, time_axis if time_axis < average_axis else time_axis - 1)
+        if tuple(rr.shape[:-1]) != vox:
+            raise ValueError(f"reference shape {tuple(reference.shape)} does not match x {tuple(x.shape)} off the "
+                             "average and time axes")
+        stride = rr.shape[-1]
+    n_ref = rr.shape[-1]
+    if not average and not want_y:
+        raise ValueError("want_y=False needs average=True")
+    dev_ = x.device
+    per = shape[:-1]
+    y = torch.empty(shape, dtype=x.dtype, device=dev_) if want_y else None
+    mean = torch.empty(vox + (n,), dtype=x.dtype, device=dev_) if average else None
+    n_avg = torch.empty(vox, dtype=torch.int32, device=dev_) if average else None
+    shift = torch.empty(per, dtype=torch.float64, device=dev_)
+    phase = torch.empty(per, dtype=torch.float64, device=dev_)
+    quality = torch.empty(per, dtype=torch.float64, device=dev_)
+    status = torch.empty(per, dtype=torch.int32, device=dev_)
+    work = workspace if workspace is not None else torch.zeros(_lib.XM_ALIGN_WORKSPACE_BYTES, dtype=torch.uint8, device=dev_)
+    for k in _skip:
+        code |= ALIGN_SKIP[k]
+    ptr = lambda t_: t_.data_ptr() if t_ is not None else None  # noqa: E731
+    _lib.call("xm_align_rows", xr.data_ptr(), rr.data_ptr(), stride, ptr(y), ptr(mean), shift.data_ptr(),
+              phase.data_ptr(), quality.data_ptr(), status.data_ptr(), ptr(n_avg), n_outer, a_, n_inner, n, n_ref,
+              int(n_points), float(dt), float(t0), float(max_shift), float(min_quality), code, work.data_ptr(), _stream(x))
+    return AlignRows(y=y, mean=mean, shift=shift, phase=phase, quality=quality, status=status, n_averaged=n_avg)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 

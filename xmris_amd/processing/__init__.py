@@ -1,11 +1,12 @@
 """GPU implementations of the reference's ``xmris.processing`` functions on the spectral hot path."""
+from .align import align_averages
 from .baseline import baseline_als
 from .coils import combine_coils
 from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
 from .phasing import autophase, autophase_each, phase
 
-__all__ = ["baseline_als", "combine_coils", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
+__all__ = ["align_averages", "baseline_als", "combine_coils", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
