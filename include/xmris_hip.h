@@ -310,6 +310,35 @@ int xm_align_rows(const void* x, const void* r, int64_t r_voxel_stride, void* y,
                   int64_t n_inner, int N, int N_r, int L, double dt, double t0, double max_shift, double min_quality,
                   int dtype, void* workspace, void* stream);
 
+/* ---- residual-signal (water) removal by HSVD (this backend's own definition, the reference has
+ * none).  `x`: n_batch rows of N samples, row_stride elements apart.  Per row, all in fp64: H[l][j] = x[l + j], N - M + 1
+ * rows and M columns; G = H^H H; W = conj(U), U the eigenvectors of G's K largest eigenvalues (a tie going to the lower
+ * index); Q = (I + w w^H / (1 - ||w||^2)) W[0:M-1]^H W[1:M], w^H the last row of W (the least-squares shift matrix);
+ * z_k = eig(Q) (Hessenberg form, shifted QR), f_k = arg(z_k) / (2 pi dt), d_k = -ln|z_k| / dt, sorted by f_k ascending; a
+ * minimises sum_{t<N} |x_t - sum_k a_k z_k^t|^2 with z_k^t = exp(t log z_k) per point (normal equations, Cholesky);
+ * y_t = x_t - sum of a_k z_k^t over the k with f_lo <= f_k <= f_hi, rounded once to the input's dtype.  Outputs
+ * (device): y (n_batch, N) of the input's dtype, or NULL for the components alone; freq (Hz), damp (1/s), amp = |a_k|,
+ * phase = arg a_k (rad), removed (0 / 1), each (n_batch, K); n_removed and status per row: 0 done; 1 no pole in the band
+ * (y = x bitwise), or x all zero (y = x, components NaN); 2 a non-finite sample, or samples so large that G or its squared
+ * norm overflows: y zero, components NaN; 3 the Jacobi sweep cap (30) or the QR iteration cap (30 K) was reached: y = x,
+ * components NaN; 4 1 - ||w||^2 <= 0, a pole that is zero or not finite, a z_k^t that is not finite, or a pivot of the
+ * amplitude system that is not positive and finite: y = x, components NaN.  `dtype`: XM_C64 / XM_C128;
+ * XM_HSVD_GRAM_FMA on top of it forms G on plain FMAs instead of the matrix cores (not a user option: what the tests and
+ * the timing script hold the matrix-core form against); XM_HSVD_STOP_* end every row after the named stage (timing
+ * only: status 0, components NaN, y untouched).  `workspace`: XM_HSVD_WORKSPACE_BYTES of device memory, zero on entry to
+ * the first call and left zero by every call.  2 <= M <= 64, 1 <= K <= min(M - 1, 32), 2 M <= N <= 16384,
+ * row_stride >= N, dt > 0, finite f_lo <= f_hi, a known dtype and non-NULL pointers other than y: otherwise
+ * XM_ERR_INVALID_ARG before any HIP call. */
+#define XM_HSVD_WORKSPACE_BYTES 256
+#define XM_HSVD_GRAM_FMA 0x100
+#define XM_HSVD_STOP_GRAM 0x200
+#define XM_HSVD_STOP_EIG 0x400
+#define XM_HSVD_STOP_POLES 0x600
+#define XM_HSVD_STOP_AMPL 0x800
+int xm_hsvd_rows(const void* x, int64_t row_stride, void* y_or_null, double* freq, double* damp, double* amp,
+                 double* phase, int32_t* removed, int32_t* n_removed, int32_t* status, int64_t n_batch, int N, int M,
+                 int K, double dt, double f_lo, double f_hi, int dtype, void* workspace, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -30,6 +30,13 @@ XM_ALIGN_SKIP_COARSE = 0x100
 XM_ALIGN_SKIP_REFINE = 0x200
 XM_ALIGN_SKIP_APPLY = 0x400
 
+XM_HSVD_WORKSPACE_BYTES = 256
+XM_HSVD_GRAM_FMA = 0x100
+XM_HSVD_STOP_GRAM = 0x200
+XM_HSVD_STOP_EIG = 0x400
+XM_HSVD_STOP_POLES = 0x600
+XM_HSVD_STOP_AMPL = 0x800
+
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
 XM_ERR_HIP = -3
@@ -72,6 +79,8 @@ SIGNATURES = {
     "xm_align_workspace_bytes": (_l, [_l, _i, _l, _i]),
     "xm_align_rows": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _i, ctypes.c_double, ctypes.c_double,
                            ctypes.c_double, ctypes.c_double, _i, _p, _p]),
+    "xm_hsvd_rows": (_i, [_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, ctypes.c_double, ctypes.c_double,
+                          ctypes.c_double, _i, _p, _p]),
     "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

@@ -65,6 +65,14 @@ class XmrisProcessingMixin:
         return combine_coils(self._obj, dim=dim, time_dim=time_dim, method=method, reference=reference,
                              noise_cov=noise_cov, n_points=n_points, return_weights=return_weights)
 
+    def remove_water(self, dim: str = DIMS.time, band=(-50.0, 50.0), rank: int = 20, n_cols: int = 64, dt: float = None,
+                     return_components: bool = False):
+        """Per-voxel HSVD removal of the residual water signal on the GPU (an addition of this backend)."""
+        from .processing.water import remove_water
+
+        return remove_water(self._obj, dim=dim, band=band, rank=rank, n_cols=n_cols, dt=dt,
+                            return_components=return_components)
+
     def align_averages(self, dim: str = DIMS.average, time_dim: str = DIMS.time, reference="mean", max_shift: float = 20.0,
                        t_max: float = None, n_points: int = None, passes: int = 1, average: bool = False,
                        min_quality: float = 0.0, return_shifts: bool = False):

@@ -58,6 +58,9 @@ class _Attrs(_Vocabulary):
     align_dim = XmrisTerm("align_dim", "Name of the dimension whose transients were frequency- and phase-aligned.")
     align_reference = XmrisTerm("align_reference", "What the transients were aligned to: 'mean', 'first', an index or 'array'.")
     align_max_shift = XmrisTerm("align_max_shift", "Largest frequency shift the alignment searched.", "Hz")
+    water_band = XmrisTerm("water_band", "Frequency band whose HSVD components were removed.", "Hz")
+    water_rank = XmrisTerm("water_rank", "Number of damped exponentials of the HSVD model.")
+    water_n_cols = XmrisTerm("water_n_cols", "Columns of the HSVD Hankel matrix.")
 
 
 class _Dims(_Vocabulary):

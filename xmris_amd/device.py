@@ -550,6 +550,69 @@ def align_rows(x, average_axis: int, time_axis: int, reference, n_points: int, d
     return AlignRows(y=y, mean=mean, shift=shift, phase=phase, quality=quality, status=status, n_averaged=n_avg)
 
 
+class HsvdRows:
+    """Raw outputs of ``hsvd_rows``, the input's axes other than time in front and in the input's order: y like x (time
+    last) or None; frequency (Hz), damping (1/s), amplitude, phase (rad) fp64 and removed int32, each [..., K], sorted
+    by frequency; n_removed and status int32 per row (0 done, 1 nothing in the band or an all-zero row, 2 non-finite,
+    3 iteration cap, 4 degenerate poles or amplitudes)."""
+
+    __slots__ = ("y", "frequency", "damping", "amplitude", "phase", "removed", "n_removed", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+HSVD_MAX_COLS = 64
+HSVD_MAX_RANK = 32
+HSVD_MAX_POINTS = 16384
+HSVD_STOP = {"gram": _lib.XM_HSVD_STOP_GRAM, "eig": _lib.XM_HSVD_STOP_EIG, "poles": _lib.XM_HSVD_STOP_POLES,
+             "ampl": _lib.XM_HSVD_STOP_AMPL}
+
+
+def hsvd_rows(x, time_axis: int, n_cols: int, rank: int, dt: float, band, want_y: bool = True, workspace=None,
+              _gram_fma: bool = False, _stop=None) -> HsvdRows:
+    """HSVD of every row of the complex64 / complex128 device tensor `x` along `time_axis` and removal of the components
+    whose frequency lies in `band` = (f_lo, f_hi) Hz, in one launch (xm_hsvd_rows).  With time as
+    the last axis the kernel reads the rows where they lie (one row stride; a tensor whose rows are not evenly spaced is
+    copied); a time axis that is not last costs one contiguous copy.  `want_y=False`: the components alone.
+    `_gram_fma` (tests and timing only): the Gram matrix on plain FMAs; `_stop`: end after "gram", "eig", "poles" or
+    "ampl" (timing only)."""
+    torch = _torch()
+    _require_device(x)
+    nd = x.dim()
+    time_axis = time_axis % nd
+    xr = torch.movedim(x, time_axis, -1) if time_axis != nd - 1 else x
+    n = xr.shape[-1]
+    lead = tuple(xr.shape[:-1])
+    code = _dtype_code(xr)
+    if xr.dim() == 2 and xr.stride(1) == 1 and xr.stride(0) >= n:
+        stride = xr.stride(0)  # rows of a wider buffer, read in place
+    else:
+        xr = xr if xr.is_contiguous() else xr.contiguous()
+        stride = n
+    nb = int(np.prod(lead, dtype=np.int64))
+    k = int(rank)
+    dev_ = x.device
+    y = torch.empty(lead + (n,), dtype=x.dtype, device=dev_) if want_y else None
+    f64 = lambda: torch.empty(lead + (k,), dtype=torch.float64, device=dev_)  # noqa: E731
+    freq, damp, amp, phase = f64(), f64(), f64(), f64()
+    removed = torch.empty(lead + (k,), dtype=torch.int32, device=dev_)
+    n_removed = torch.empty(lead, dtype=torch.int32, device=dev_)
+    status = torch.empty(lead, dtype=torch.int32, device=dev_)
+    work = workspace if workspace is not None else torch.zeros(_lib.XM_HSVD_WORKSPACE_BYTES, dtype=torch.uint8, device=dev_)
+    if _gram_fma:
+        code |= _lib.XM_HSVD_GRAM_FMA
+    if _stop is not None:
+        code |= HSVD_STOP[_stop]
+    _lib.call("xm_hsvd_rows", xr.data_ptr(), int(stride), y.data_ptr() if y is not None else None, freq.data_ptr(),
+              damp.data_ptr(), amp.data_ptr(), phase.data_ptr(), removed.data_ptr(), n_removed.data_ptr(),
+              status.data_ptr(), nb, int(n), int(n_cols), k, float(dt), float(band[0]), float(band[1]), code,
+              work.data_ptr(), _stream(x))
+    return HsvdRows(y=y, frequency=freq, damping=damp, amplitude=amp, phase=phase, removed=removed,
+                    n_removed=n_removed, status=status)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
