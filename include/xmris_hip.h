@@ -339,6 +339,32 @@ int xm_hsvd_rows(const void* x, int64_t row_stride, void* y_or_null, double* fre
                  double* phase, int32_t* removed, int32_t* n_removed, int32_t* status, int64_t n_batch, int N, int M,
                  int K, double dt, double f_lo, double f_hi, int dtype, void* workspace, void* stream);
 
+/* ---- Marchenko-Pastur patch PCA denoising (this backend's own definition, the reference has
+ * none).  The data are viewed as (n_outer, s1, s2, s3, N), C-contiguous, time last; a patch dim that is not used has size
+ * and patch size 1.  Per voxel i = (i1, i2, i3), all in fp64: the window starts at o_a = min(max(i_a - p_a / 2, 0),
+ * s_a - p_a) in every patch dim (integer division; always full, shifted inward at an edge); X = the P x N matrix of the
+ * window's FIDs, P = p1 p2 p3, rows in row-major order of the window offsets, c the row that is voxel i; G = X X^H;
+ * lambda_k = max(eig_k, 0) / N descending (a tie going to the lower index), U the matching eigenvectors.  Rank r: `rank`
+ * when it is >= 0; with rank = -1 the first p in 0 ... P - 1 with (lambda_p - lambda_{P-1}) / (4 sqrt((P - p) / N)) <
+ * (sum_{i>=p} lambda_i) / (P - p), the sum accumulated from i = P - 1 downwards, and P when no p qualifies.
+ * w_j = sum_{k<r} U[c][k] conj(U[j][k]); y_i[t] = sum_j w_j X[j][t] in ascending j, rounded once to the input's dtype;
+ * only voxel i's own row is written.  Outputs (device): y as x (must not be x: the windows overlap); rank_out (int32),
+ * sigma = sqrt(mean(lambda_r ... lambda_{P-1})) (0 when r = P; the standard deviation of the complex noise) and status
+ * per voxel: 0 done; 1 the window is all zero: y zero, rank 0, sigma 0; 2 a non-finite sample in the window, or samples
+ * so large that G or its squared norm overflows: y zero, rank 0, sigma NaN; 3 the Jacobi sweep cap (30) was reached:
+ * y = x for this voxel, rank 0, sigma NaN.  `dtype`: XM_C64 / XM_C128; XM_DENOISE_GRAM_FMA on top of it forms G on plain
+ * FMAs at every P instead of the matrix cores (P >= 8; not a user option: what the tests and the timing script hold the
+ * matrix-core form against); XM_DENOISE_STOP_* end every voxel after the named stage (timing only: status 0, y
+ * untouched).  `workspace`: XM_DENOISE_WORKSPACE_BYTES of device memory, zero on entry to the first call and left zero
+ * by every call.  1 <= p_a <= s_a, 2 <= P <= 64, P <= N <= 16384, -1 <= rank <= P, n_outer >= 0, at most 2^32 - 1
+ * voxels, a known dtype, non-NULL pointers and y != x: otherwise XM_ERR_INVALID_ARG before any HIP call. */
+#define XM_DENOISE_WORKSPACE_BYTES 256
+#define XM_DENOISE_GRAM_FMA 0x100
+#define XM_DENOISE_STOP_GRAM 0x200
+#define XM_DENOISE_STOP_EIG 0x400
+int xm_denoise_patches(const void* x, void* y, int32_t* rank_out, double* sigma, int32_t* status, int64_t n_outer, int s1,
+                       int s2, int s3, int p1, int p2, int p3, int N, int rank, int dtype, void* workspace, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -37,6 +37,11 @@ XM_HSVD_STOP_EIG = 0x400
 XM_HSVD_STOP_POLES = 0x600
 XM_HSVD_STOP_AMPL = 0x800
 
+XM_DENOISE_WORKSPACE_BYTES = 256
+XM_DENOISE_GRAM_FMA = 0x100
+XM_DENOISE_STOP_GRAM = 0x200
+XM_DENOISE_STOP_EIG = 0x400
+
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
 XM_ERR_HIP = -3
@@ -81,6 +86,7 @@ SIGNATURES = {
                            ctypes.c_double, ctypes.c_double, _i, _p, _p]),
     "xm_hsvd_rows": (_i, [_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, _i, _p, _p]),
+    "xm_denoise_patches": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

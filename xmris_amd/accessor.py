@@ -73,6 +73,12 @@ class XmrisProcessingMixin:
         return remove_water(self._obj, dim=dim, band=band, rank=rank, n_cols=n_cols, dt=dt,
                             return_components=return_components)
 
+    def denoise_mppca(self, dims, patch, time_dim: str = DIMS.time, rank=None, return_noise: bool = False):
+        """Marchenko-Pastur patch PCA denoising on the GPU (an addition of this backend)."""
+        from .processing.denoise import denoise_mppca
+
+        return denoise_mppca(self._obj, dims, patch, time_dim=time_dim, rank=rank, return_noise=return_noise)
+
     def align_averages(self, dim: str = DIMS.average, time_dim: str = DIMS.time, reference="mean", max_shift: float = 20.0,
                        t_max: float = None, n_points: int = None, passes: int = 1, average: bool = False,
                        min_quality: float = 0.0, return_shifts: bool = False):

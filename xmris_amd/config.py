@@ -61,6 +61,9 @@ class _Attrs(_Vocabulary):
     water_band = XmrisTerm("water_band", "Frequency band whose HSVD components were removed.", "Hz")
     water_rank = XmrisTerm("water_rank", "Number of damped exponentials of the HSVD model.")
     water_n_cols = XmrisTerm("water_n_cols", "Columns of the HSVD Hankel matrix.")
+    denoise_dims = XmrisTerm("denoise_dims", "Names of the dimensions the denoising patch extends over.")
+    denoise_patch = XmrisTerm("denoise_patch", "Patch size along each of the denoising dimensions.")
+    denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 
 class _Dims(_Vocabulary):

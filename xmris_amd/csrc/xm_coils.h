@@ -1,5 +1,5 @@
 // Coil combination kernel (the project's own definition, the reference has no such function).
-// Included by xm_coils.hip only.
+// Included by xm_coils.hip, and by xm_denoise.h for the staging, Gram, mirror, sum and Jacobi functions.
 //
 // One voxel: X = its C x N FIDs (coil by time), R = the same voxel of the reference (or X), Linv = L^{-1} of the noise
 // covariance Psi = L L^H (or the identity).  G = Linv (R R^H) Linv^H; u = the eigenvector of G's largest eigenvalue
@@ -90,13 +90,16 @@ XM_DEV double cc_sum(const CcLds& L, double v) {
   return r;
 }
 
-// tile [t0, t0 + Q) of R into Y (the B matrix); flags: bit 0 a non-finite sample, bit 1 a nonzero one
-XM_DEV void cc_stage(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int t0, int& flags) {
+// tile [t0, t0 + Q) of R into Y (the B matrix); flags: bit 0 a non-finite sample, bit 1 a nonzero one.  GATHER
+// (k_denoise, xm_denoise.h): row c starts at rows[c], a table in the LDS, instead of V.roff + c V.rcs
+template <bool GATHER = false>
+XM_DEV void cc_stage(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int t0, int& flags,
+                     const long long* rows = nullptr) {
   const int t = threadIdx.x, tt = t & (XM_CC_Q - 1), Cp = cc_pad8(A.C);
   for (int c = t / XM_CC_Q; c < Cp; c += XM_CC_NT / XM_CC_Q) {
     double re = 0.0, im = 0.0;
     if (c < A.C && t0 + tt < A.NR) {
-      cc_load(A.ref, A.is_c128, V.roff + c * V.rcs + t0 + tt, re, im);
+      cc_load(A.ref, A.is_c128, (GATHER ? rows[c] : V.roff + c * V.rcs) + t0 + tt, re, im);
       if (!isfinite(re) || !isfinite(im)) flags |= 1;
       if (re != 0.0 || im != 0.0) flags |= 2;
     }
@@ -120,7 +123,9 @@ XM_DEV void cc_mirror(const CcLds& L, int C) {
 }
 
 // G <- R R^H by plain FMAs: thread t owns entries t + 256 m of the upper triangle in row-major order
-XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags) {
+template <bool GATHER = false>
+XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags,
+                        const long long* rows = nullptr) {
   const int t = threadIdx.x, C = A.C, ne = C * (C + 1) / 2;
   int ci[XM_CC_MAXE], cj[XM_CC_MAXE];
   double re[XM_CC_MAXE], im[XM_CC_MAXE];
@@ -142,7 +147,7 @@ XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int
     }
   }
   for (int t0 = 0; t0 < A.NR; t0 += XM_CC_Q) {
-    cc_stage(A, L, V, t0, flags);
+    cc_stage<GATHER>(A, L, V, t0, flags, rows);
     __syncthreads();
 #pragma unroll
     for (int m = 0; m < XM_CC_MAXE; ++m) {
@@ -173,7 +178,9 @@ XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int
 // Y Y^T; slice: a quarter of each tile's points when nblk < 4, else the whole tile); wave v takes items v, v + 4, ...
 // Operands of v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], i.e. Y[16 I + (l & 15)][k]
 // and Y[16 J + (l & 15)][k] with k = 4 kk + (l >> 4); result r of lane l is row (l >> 4) + 4 r, column l & 15.
-XM_DEV void cc_gram_mfma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags) {
+template <bool GATHER = false>
+XM_DEV void cc_gram_mfma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags,
+                         const long long* rows = nullptr) {
   const int t = threadIdx.x, C = A.C, wave = t >> 6, lane = t & 63;
   const int nb = cc_pad8(C) / 8, nblk = nb * (nb + 1) / 2, S = nblk < 4 ? 4 : 1, nitems = nblk * S;
   const int ksteps = XM_CC_Q / 4 / S;
@@ -194,7 +201,7 @@ XM_DEV void cc_gram_mfma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, in
     acc[m] = cc_d4{0.0, 0.0, 0.0, 0.0};
   }
   for (int t0 = 0; t0 < A.NR; t0 += XM_CC_Q) {
-    cc_stage(A, L, V, t0, flags);
+    cc_stage<GATHER>(A, L, V, t0, flags, rows);
     __syncthreads();
 #pragma unroll
     for (int m = 0; m < XM_CC_MAXB; ++m) {

@@ -613,6 +613,74 @@ def hsvd_rows(x, time_axis: int, n_cols: int, rank: int, dt: float, band, want_y
                     n_removed=n_removed, status=status)
 
 
+class DenoisePatches:
+    """Raw outputs of ``denoise_patches`` in the input's axis order: y like x; rank int32, sigma fp64 and status int32
+    per voxel, i.e. with x's axes other than time (0 done, 1 all-zero window, 2 non-finite sample, 3 Jacobi sweep cap)."""
+
+    __slots__ = ("y", "rank", "sigma", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+DENOISE_MAX_PATCH = 64
+DENOISE_MAX_POINTS = 16384
+DENOISE_STOP = {"gram": _lib.XM_DENOISE_STOP_GRAM, "eig": _lib.XM_DENOISE_STOP_EIG}
+
+
+def denoise_patches(x, patch_axes, time_axis: int, patch, rank=None, workspace=None, _gram_fma: bool = False,
+                    _stop=None) -> DenoisePatches:
+    """Marchenko-Pastur patch PCA denoising of the complex64 / complex128 device tensor `x` in one launch
+    (xm_denoise_patches).  `patch_axes`: 1 ... 3 axes the window extends over, `patch`: its size
+    along each; every other axis but `time_axis` is batch.  `rank`: the number of components kept, or None for the
+    Marchenko-Pastur rule.  With the patch axes adjacent, in the given order and right in front of a last time axis the
+    kernel addresses the tensor where it lies; any other layout costs one contiguous copy.  `_gram_fma` (tests and
+    timing only): the Gram matrix on plain FMAs at every patch size; `_stop`: end after "gram" or "eig" (timing only)."""
+    torch = _torch()
+    _require_device(x)
+    nd = x.dim()
+    time_axis = time_axis % nd
+    axes = [int(a) % nd for a in patch_axes]
+    patch = [int(p) for p in patch]
+    if not 1 <= len(axes) <= 3:
+        raise ValueError(f"patch_axes: needs 1 ... 3 axes, got {len(axes)}")
+    if len(set(axes)) != len(axes) or time_axis in axes:
+        raise ValueError("patch_axes must differ from each other and from time_axis")
+    if len(patch) != len(axes):
+        raise ValueError(f"patch: needs one size per patch axis ({len(axes)}), got {len(patch)}")
+    batch = [a for a in range(nd) if a != time_axis and a not in axes]
+    perm = batch + axes + [time_axis]
+    xr = x.permute(perm) if perm != list(range(nd)) else x
+    xr = xr if xr.is_contiguous() else xr.contiguous()
+    shape = tuple(xr.shape)
+    n = shape[-1]
+    sizes = [1] * (3 - len(axes)) + list(shape[len(batch):-1])
+    pp = [1] * (3 - len(axes)) + patch
+    n_outer = int(np.prod(shape[:len(batch)], dtype=np.int64))
+    code = _dtype_code(xr)
+    dev_ = x.device
+    y = torch.empty(shape, dtype=x.dtype, device=dev_)
+    rk = torch.empty(shape[:-1], dtype=torch.int32, device=dev_)
+    sigma = torch.empty(shape[:-1], dtype=torch.float64, device=dev_)
+    status = torch.empty(shape[:-1], dtype=torch.int32, device=dev_)
+    work = workspace if workspace is not None else torch.zeros(_lib.XM_DENOISE_WORKSPACE_BYTES, dtype=torch.uint8, device=dev_)
+    if _gram_fma:
+        code |= _lib.XM_DENOISE_GRAM_FMA
+    if _stop is not None:
+        code |= DENOISE_STOP[_stop]
+    _lib.call("xm_denoise_patches", xr.data_ptr(), y.data_ptr(), rk.data_ptr(), sigma.data_ptr(), status.data_ptr(),
+              n_outer, sizes[0], sizes[1], sizes[2], pp[0], pp[1], pp[2], int(n), -1 if rank is None else int(rank), code,
+              work.data_ptr(), _stream(x))
+    if perm != list(range(nd)):  # back to the input's axis order
+        inv = [perm.index(a) for a in range(nd)]
+        vperm = [a for a in perm if a != time_axis]
+        vinv = [vperm.index(a) for a in range(nd) if a != time_axis]
+        y = y.permute(inv)
+        rk, sigma, status = rk.permute(vinv), sigma.permute(vinv), status.permute(vinv)
+    return DenoisePatches(y=y, rank=rk, sigma=sigma, status=status)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
