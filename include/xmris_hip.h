@@ -365,6 +365,18 @@ int xm_hsvd_rows(const void* x, int64_t row_stride, void* y_or_null, double* fre
 int xm_denoise_patches(const void* x, void* y, int32_t* rank_out, double* sigma, int32_t* status, int64_t n_outer, int s1,
                        int s2, int s3, int p1, int p2, int p3, int N, int rank, int dtype, void* workspace, void* stream);
 
+/* ---- MRSI spatial reconstruction: a small dense matrix along one axis (this backend's own
+ * definition, the reference has none beyond zero_fill + ifftc).  x is viewed as (n_outer, n, n_inner) and y as (n_outer,
+ * m, n_inner), both C-contiguous: any axis of a contiguous tensor is such a view, so nothing is transposed.  `table`:
+ * m x n complex128, row-major, in device memory.  y[o][p][i] = sum_j table[p][j] x[o][j][i], the products and the sum in
+ * fp64 (ascending j, every step a fused multiply-add), rounded once to `dtype` (XM_C64 / XM_C128).  The kernel applies a
+ * general matrix: filter, zero fill, voxel shift, the centring rolls and the ortho scale of to_image / to_kspace are all
+ * in the table the host builds.  A pencil (o, i) depends on its own n samples only.  1 <= n, m <= 64, n_outer, n_inner
+ * >= 0, at most 2^50 pencils, non-NULL pointers, y != x and a known dtype: otherwise XM_ERR_INVALID_ARG before any HIP
+ * call.  n_outer = 0 or n_inner = 0 launches nothing. */
+int xm_axis_dft(const void* x, void* y, const void* table, int64_t n_outer, int n, int m, int64_t n_inner, int dtype,
+                void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

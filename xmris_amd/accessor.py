@@ -127,6 +127,21 @@ class XmrisFusedMixin:
                                  method=method, peak_width=peak_width, **kwargs)
 
 
+class XmrisMrsiMixin:
+    def to_image(self, dim=(DIMS.kx, DIMS.ky), out_dim=None, matrix=None, filter=None, shift=None):
+        """k-space to voxels: filter, zero fill, voxel shift and centred inverse transform, one launch per dim (an
+        addition of this backend)."""
+        from .processing.mrsi import to_image
+
+        return to_image(self._obj, dim=dim, out_dim=out_dim, matrix=matrix, filter=filter, shift=shift)
+
+    def to_kspace(self, dim=(DIMS.x, DIMS.y), out_dim=None, matrix=None, filter=None, shift=None):
+        """Voxels to k-space: the forward counterpart of ``to_image``."""
+        from .processing.mrsi import to_kspace
+
+        return to_kspace(self._obj, dim=dim, out_dim=out_dim, matrix=matrix, filter=filter, shift=shift)
+
+
 class XmrisFittingMixin:
     def fit_amares(self, prior_knowledge_file, dim: str = "time", mhz: float = None, sw: float = None,
                    deadtime: float = None, method: str = "leastsq", initialize_with_lm: bool = True,
@@ -139,7 +154,7 @@ class XmrisFittingMixin:
 
 
 class XmrisAccessor(XmrisFourierMixin, XmrisProcessingMixin, XmrisPhasingMixin, XmrisVendorMixin, XmrisFusedMixin,
-                    XmrisFittingMixin):
+                    XmrisFittingMixin, XmrisMrsiMixin):
     """``obj.xmr.<method>`` for the hot-path methods."""
 
     def __init__(self, obj):

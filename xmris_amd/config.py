@@ -63,6 +63,10 @@ class _Attrs(_Vocabulary):
     water_n_cols = XmrisTerm("water_n_cols", "Columns of the HSVD Hankel matrix.")
     denoise_dims = XmrisTerm("denoise_dims", "Names of the dimensions the denoising patch extends over.")
     denoise_patch = XmrisTerm("denoise_patch", "Patch size along each of the denoising dimensions.")
+    mrsi_dims = XmrisTerm("mrsi_dims", "Names of the dimensions the spatial reconstruction transformed, as they were before it.")
+    mrsi_matrix = XmrisTerm("mrsi_matrix", "Points along each transformed dimension after the reconstruction (the interpolated matrix).")
+    mrsi_filter = XmrisTerm("mrsi_filter", "Spatial filter of the reconstruction: 'none', 'hamming', 'hann' or 'custom'.")
+    mrsi_shift = XmrisTerm("mrsi_shift", "Shift applied along each transformed dimension.", "output points")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 

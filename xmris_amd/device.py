@@ -681,6 +681,43 @@ def denoise_patches(x, patch_axes, time_axis: int, patch, rank=None, workspace=N
     return DenoisePatches(y=y, rank=rk, sigma=sigma, status=status)
 
 
+AXIS_DFT_MAX = 64
+
+
+def axis_dft(x, axis: int, table):
+    """``y = table @ x`` along `axis` of the complex64 / complex128 device tensor `x` in one launch (xm_axis_dft,
+    DESIGN.md section 14): `table` is [m, n] complex (host values or a device tensor; uploaded as complex128), n the
+    size of `axis`, 1 <= n, m <= 64; the products and sums are fp64 and round once to x's dtype.  Any axis of a
+    contiguous tensor is read where it lies; a tensor that is not contiguous costs one contiguous copy.  Returns a new
+    tensor with m points along `axis`; `x` is left untouched."""
+    _require_device(x)
+    torch = _torch()
+    code = _dtype_code(x)
+    nd = x.dim()
+    if nd == 0:
+        raise ValueError("axis_dft needs at least one axis")
+    axis = axis % nd
+    if isinstance(table, torch.Tensor):
+        t = table.to(device=x.device, dtype=torch.complex128).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(table, dtype=np.complex128))).to(x.device)
+    n = x.shape[axis]
+    if t.dim() != 2 or t.shape[1] != n:
+        raise ValueError(f"table must be [m, {n}] for an axis of {n} points, got {tuple(t.shape)}")
+    m = int(t.shape[0])
+    xc = x if x.is_contiguous() else x.contiguous()
+    shape = tuple(xc.shape)
+    n_outer = int(np.prod(shape[:axis], dtype=np.int64))
+    n_inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    out = torch.empty(shape[:axis] + (m,) + shape[axis + 1:], dtype=x.dtype, device=x.device)
+    if n == 0:
+        raise ValueError("axis_dft needs at least one point along the axis")
+    if out.numel() == 0:
+        return out
+    _lib.call("xm_axis_dft", xc.data_ptr(), out.data_ptr(), t.data_ptr(), n_outer, int(n), m, n_inner, code, _stream(x))
+    return out
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
