@@ -258,6 +258,34 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
                          double* amp_sd, double* rss, int32_t* status, int32_t* iters, void* fit_data, void* workspace,
                          int64_t workspace_bytes, int dtype, void* stream);
 
+/* ---- quantification: basis-set (linear-combination) fitting (this backend's own definition).
+ * Model: x^_n = e^{i phi} sum_m a_m B_m[n] exp(-d_g t_n - s_g t_n^2 + i 2 pi f_g t_n), g = group[m], t_n = n dt; the
+ * cost is the sum over n >= skip of |x_n - x^_n|^2.  `basis`: device, [n_metab, n] complex128, shared by every row.
+ * `group`: HOST array of n_metab indices in 0 ... n_groups - 1, no group empty.  A row has Q = n_metab + 3 n_groups + 1
+ * parameters, fp64: a_m at m, then the shifts f_g [Hz], the Lorentzian dampings d_g [1/s], the Gaussian dampings s_g
+ * [1/s^2], then phi [rad].
+ *
+ * xm_basis_model: out[b, j] (complex128) = x^_j for the parameters params[b, :] ([n_batch, Q], device). */
+int xm_basis_model(const double* params, int64_t n_batch, const void* basis, int n_metab, const int32_t* group,
+                   int n_groups, int n, double dt, void* out, void* stream);
+/* xm_basis_fit: one Levenberg-Marquardt fit per row of `in`, iteration, stopping rules and status codes as
+ * xm_amares_fit.  HOST arrays of Q values: `init` (clipped into its bounds; NaN for a free amplitude: the automatic
+ * start ||x|| / (n_metab ||B_m||), norms over the fitted points, per row), `lower` / `upper` (+-inf: unbounded side,
+ * amplitudes and phi only: a free f, d or s needs two finite bounds), `fixed` (nonzero, or lower == upper: held).
+ * Outputs (device): params[n_batch, Q] physical, amp_sd[n_batch, n_metab] = sqrt of the amplitude's diagonal entry of
+ * (J^T J)^{-1} over the physical free parameters (the caller scales by sigma; 0 for a fixed amplitude, NaN when J^T J
+ * is singular), rss, status, iters [n_batch]; `fit_data` (may be NULL): [n_batch, n] complex128 model at the solution,
+ * all n points.  Status 2: params, amp_sd and fit_data zero, rss NaN.  `workspace`: xm_basis_workspace_bytes() bytes of
+ * device memory whose first 8 bytes are zero between calls (the kernel leaves them so).  XM_ERR_INVALID_ARG before any
+ * HIP call, outputs and counters untouched: a group index out of range or an empty group, n_metab < 1, Q > 128, more
+ * than 80 free parameters P, n - skip < P, a NaN bound, lower > upper, an infinite bound of a free f, d or s. */
+int64_t xm_basis_workspace_bytes(int64_t n_batch, int n, int n_metab);
+int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, double dt, int skip, const void* basis,
+                 int n_metab, const int32_t* group, int n_groups, const double* init, const double* lower,
+                 const double* upper, const int32_t* fixed, int max_iter, double ftol, double xtol, double* params,
+                 double* amp_sd, double* rss, int32_t* status, int32_t* iters, void* fit_data, void* workspace,
+                 int64_t workspace_bytes, int dtype, void* stream);
+
 /* ---- coil combination (this backend's own definition, the reference has none).
  * The data are viewed as (n_outer, C, n_inner, N), C-contiguous: voxel (a, b) holds the C x N matrix X of its FIDs, its
  * coils n_inner N elements apart.  `ref_or_null`: the reference R, (n_outer, C, n_inner, N_R) of the same dtype, or NULL

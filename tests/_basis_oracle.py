@@ -1,0 +1,308 @@
+"""Independent numpy / scipy statement of the basis-set estimator of DESIGN.md section 15, the yardstick of
+k_basis_fit.  It does not import xmris_amd: basis, groups and parameter arrays come in as plain arrays.
+
+A voxel has Q = M + 3 G + 1 parameters in fitting units: amplitudes a_m (index m), then per group the shift f_g [Hz]
+(M + g), the Lorentzian damping d_g [1/s] (M + G + g), the Gaussian damping s_g [1/s^2] (M + 2 G + g), then the phase
+phi [rad] (M + 3 G).  Model: x^_n = e^{i phi} sum_m a_m B_m[n] exp(-d_g t_n - s_g t_n^2 + i 2 pi f_g t_n), g = group[m],
+t_n = n dt; cost: sum over n >= skip of |x_n - x^_n|^2.  Bounds: lmfit's transforms (tests/_amares_oracle.py).
+"""
+import numpy as np
+from scipy.optimize import least_squares
+
+from _amares_oracle import from_internal, real_rows, to_internal
+
+LN2 = float(np.log(2.0))
+
+
+def gaussian_damping(fwhm_hz):
+    return (np.pi * np.asarray(fwhm_hz, dtype=np.float64)) ** 2 / (4.0 * LN2)
+
+
+def _parts(p, group):
+    group = np.asarray(group)
+    M, G = group.size, int(group.max()) + 1
+    p = np.asarray(p, dtype=np.float64)
+    assert p.size == M + 3 * G + 1, (p.size, M, G)
+    return M, G, p[:M], p[M:M + G], p[M + G:M + 2 * G], p[M + 2 * G:M + 3 * G], p[M + 3 * G]
+
+
+def _factors(p, B, group, dt):
+    """(E [n, G] complex: e^{i phi} exp(-d t - s t^2 + i 2 pi f t), t [n])."""
+    M, G, a, f, d, s, phi = _parts(p, group)
+    t = np.arange(B.shape[1]) * dt
+    tc = t[:, None]
+    return np.exp(-d * tc - s * tc * tc) * np.exp(1j * (phi + 2.0 * np.pi * f * tc)), t
+
+
+def model(p, B, group, dt):
+    """p [Q], B [M, n] complex -> complex128 FID [n] (all n points)."""
+    B = np.asarray(B, dtype=np.complex128)
+    group = np.asarray(group)
+    E, _ = _factors(p, B, group, dt)
+    a = np.asarray(p, dtype=np.float64)[:group.size]
+    return np.sum(a * E[:, group] * B.T, axis=1)
+
+
+def model_jacobian(p, B, group, dt):
+    """d model / d p: complex [n, Q]."""
+    B = np.asarray(B, dtype=np.complex128)
+    group = np.asarray(group)
+    M, G, a, f, d, s, phi = _parts(p, group)
+    E, t = _factors(p, B, group, dt)
+    ja = E[:, group] * B.T  # [n, M]
+    T = np.stack([np.sum((a * ja)[:, group == g], axis=1) for g in range(G)], axis=1)  # [n, G]
+    tc = t[:, None]
+    return np.concatenate([ja, 2j * np.pi * tc * T, -tc * T, -tc * tc * T, 1j * np.sum(T, axis=1, keepdims=True)], axis=1)
+
+
+def automatic_amplitudes(x, B, skip=0):
+    """||x||_2 / (M ||B_m||_2), both norms over the points n >= skip; 0 for a basis function that vanishes there."""
+    x = np.asarray(x, dtype=np.complex128)[skip:]
+    Bs = np.asarray(B, dtype=np.complex128)[:, skip:x.size + skip]
+    bn = np.sqrt(np.sum(np.abs(Bs) ** 2, axis=1))
+    xn = np.sqrt(np.sum(np.abs(x) ** 2))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(bn > 0, xn / (B.shape[0] * bn), 0.0)
+
+
+def _split(lo, hi, fixed):
+    lo, hi = (np.asarray(v, dtype=np.float64).ravel() for v in (lo, hi))
+    fixed = np.zeros(lo.size, bool) if fixed is None else np.asarray(fixed, bool).ravel()
+    fixed = fixed | (lo == hi)
+    return lo, hi, fixed, np.flatnonzero(~fixed)
+
+
+def start_values(x, B, init, lo, hi, fixed=None, skip=0):
+    """(v0 [Q], u0 [P]): NaN amplitude starts replaced by the automatic start, everything clipped into its bounds."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    v0 = np.asarray(init, dtype=np.float64).ravel().copy()
+    auto = np.flatnonzero(np.isnan(v0[:B.shape[0]]))
+    if auto.size:
+        v0[auto] = automatic_amplitudes(x, B, skip)[auto]
+    v0 = np.clip(v0, lo, hi)
+    return v0, np.array([to_internal(v0[q], lo[q], hi[q]) for q in free])
+
+
+def physical(u, v0, lo, hi, fixed=None):
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    p, s = np.array(v0, dtype=np.float64).ravel().copy(), np.zeros(lo.size)
+    for j, q in enumerate(free):
+        p[q], s[q] = from_internal(u[j], lo[q], hi[q])
+    return p, s
+
+
+def _normal(x, B, group, dt, p, scale, free, skip):
+    jr = real_rows(model_jacobian(p, B, group, dt)[skip:, free] * scale)
+    r = real_rows((np.asarray(x, dtype=np.complex128) - model(p, B, group, dt))[skip:])
+    return jr.T @ jr, jr.T @ r, float(r @ r), jr, r
+
+
+def cost(x, B, group, dt, p, skip=0):
+    r = (np.asarray(x, dtype=np.complex128) - model(p, B, group, dt))[skip:]
+    return float(np.sum(r.real ** 2 + r.imag ** 2))
+
+
+def amplitude_sd(B, group, dt, p, lo, hi, fixed=None, skip=0):
+    """(sd [M], cond): sqrt(diag((J^T J)^{-1})) of the amplitudes over the physical free columns at p (0 for a fixed
+    amplitude, NaN when a free column vanishes), from an SVD of the column-scaled Jacobian, and the 2-norm condition
+    number of the unscaled J^T J (what the kernel factors)."""
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    jr = real_rows(model_jacobian(p, B, group, dt)[skip:, free])
+    sv = np.linalg.svd(jr, compute_uv=False)
+    with np.errstate(divide="ignore"):
+        cond = float((sv[0] / sv[-1]) ** 2) if sv[-1] > 0 else np.inf
+    c = np.linalg.norm(jr, axis=0)
+    sd = np.zeros(lo.size)
+    if np.all(c > 0):
+        _, s, vt = np.linalg.svd(jr / c, full_matrices=False)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sd[free] = np.sqrt(np.sum((vt.T / s) ** 2, axis=1)) / c
+    else:
+        sd[free] = np.nan
+    return sd[:B.shape[0]], cond
+
+
+def fit(x, B, group, dt, init, lo, hi, fixed=None, skip=0, tol=1e-14):
+    """One voxel by scipy.optimize.least_squares (MINPACK lmder through method="lm") in the internal variables with the
+    analytic Jacobian.  Returns params [Q], sd [Q] (sigma sqrt(diag((J^T J)^{-1})), physical free columns; 0 for fixed
+    ones), rss, sigma, crlb [M], snr [M], success."""
+    x = np.asarray(x, dtype=np.complex128)
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    v0, u0 = start_values(x, B, init, lo, hi, fixed, skip)
+
+    def fun(u):
+        return real_rows((x - model(physical(u, v0, lo, hi, fixed)[0], B, group, dt))[skip:])
+
+    def jac(u):
+        p, s = physical(u, v0, lo, hi, fixed)
+        return -real_rows(model_jacobian(p, B, group, dt)[skip:, free] * s[free])
+
+    sol = least_squares(fun, u0, jac=jac, method="lm", xtol=tol, ftol=tol, gtol=tol, max_nfev=4000)
+    p = physical(sol.x, v0, lo, hi, fixed)[0]
+    r = fun(sol.x)
+    rss = float(r @ r)
+    sigma = np.sqrt(rss / (r.size - free.size))
+    jr = real_rows(model_jacobian(p, B, group, dt)[skip:, free])
+    sd = np.zeros(lo.size)
+    sd[free] = sigma * np.sqrt(np.diag(np.linalg.inv(jr.T @ jr)))
+    M = B.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        crlb = np.where(p[:M] != 0, 100.0 * sd[:M] / np.abs(p[:M]), 0.0)
+    return {"params": p, "sd": sd, "rss": rss, "sigma": sigma, "crlb": crlb, "snr": p[:M] / sigma,
+            "success": bool(sol.success), "status": int(sol.status)}
+
+
+def lm_steps_basis(x, B, group, dt, init, lo, hi, fixed=None, skip=0, max_iter=200, ftol=1e-10, xtol=1e-10,
+                   solver="normal"):
+    """The iteration of DESIGN.md section 8 restated for the basis model, exactly as tests/_amares_oracle.lm_steps
+    states it for AMARES (lambda_0 = 1e-3, D_j the largest squared column norm so far, accept when the cost falls,
+    lambda *= max(1/3, 1 - (2 rho - 1)^3) and nu = 2 on acceptance, lambda *= nu and nu *= 2 on rejection, the same
+    stopping rules; `iters` counts trials).  solver: "normal" or "qr" (least squares on the augmented Jacobian).
+
+    Returns a dict: params [Q], u, rss, iters, status, trials (list of (accepted, (F - Ft) / F)), path [Q]."""
+    x = np.asarray(x, dtype=np.complex128)
+    B = np.asarray(B, dtype=np.complex128)
+    lo, hi, fixed, free = _split(lo, hi, fixed)
+    v0, u = start_values(x, B, init, lo, hi, fixed, skip)
+    P = free.size
+    p, s = physical(u, v0, lo, hi, fixed)
+    with np.errstate(all="ignore"):
+        F = cost(x, B, group, dt, p, skip)
+    dsc = np.zeros(P)
+    lam, nu, it = 1e-3, 2.0, 0
+    status = 1 if np.isfinite(F) else 2
+    need_jac, trials, path = True, [], np.zeros(lo.size)
+    while status == 1 and it < max_iter:
+        if need_jac:
+            p, s = physical(u, v0, lo, hi, fixed)
+            H, g, _, jr, rr = _normal(x, B, group, dt, p, s[free], free, skip)
+            dsc = np.maximum(dsc, np.diag(H))
+            need_jac = False
+        it += 1
+        D = np.where(dsc > 0, dsc, 1.0)
+        try:
+            with np.errstate(all="ignore"):
+                if solver == "qr":
+                    a = np.concatenate([jr, np.diag(np.sqrt(lam * D))])
+                    dl = np.linalg.lstsq(a, np.concatenate([rr, np.zeros(P)]), rcond=None)[0]
+                else:
+                    dl = np.linalg.solve(H + lam * np.diag(D), g)
+            ok = bool(np.all(np.isfinite(dl)))
+        except np.linalg.LinAlgError:
+            ok = False
+        if not ok:
+            trials.append((False, -np.inf))
+            lam *= nu
+            nu *= 2.0
+            if not np.isfinite(lam):
+                break
+            continue
+        dn = np.sqrt(np.sum(D * dl * dl))
+        un = np.sqrt(np.sum(D * u * u))
+        pred = float(dl @ (lam * D * dl + g))
+        xconv = dn <= xtol * (un + xtol)
+        ut = u + dl
+        pt, _ = physical(ut, v0, lo, hi, fixed)
+        with np.errstate(all="ignore"):
+            Ft = cost(x, B, group, dt, pt, skip)
+        margin = (F - Ft) / F if F > 0 and np.isfinite(Ft) else -np.inf
+        if np.isfinite(Ft) and Ft < F:
+            trials.append((True, margin))
+            rho = min(max((F - Ft) / pred, 0.0), 1.0)
+            fconv = (F - Ft) <= ftol * F
+            path += np.abs(pt - p)
+            u, F, p = ut, Ft, pt
+            q = 2.0 * rho - 1.0
+            lam *= max(1.0 / 3.0, 1.0 - q * q * q)
+            nu = 2.0
+            need_jac = True
+            if fconv or xconv:
+                status = 0
+        else:
+            trials.append((False, margin))
+            lam *= nu
+            nu *= 2.0
+            if xconv:
+                status = 0
+            if not np.isfinite(lam):
+                break
+    p = physical(u, v0, lo, hi, fixed)[0]
+    if not (np.all(np.isfinite(p)) and np.isfinite(F)):
+        status = 2
+    return {"params": p, "u": u, "rss": F, "iters": it, "status": status, "trials": trials, "path": path}
+
+
+# ---- seeded cases ---------------------------------------------------------------------------------------------------------
+def parameters(M, G, lineshape="voigt", max_shift=10.0, max_broadening=20.0, broadening_start=2.0, max_gaussian=20.0,
+               gaussian_start=2.0, fit_phase=True, amplitude_start=None):
+    """(init, lo, hi, fixed) [Q] as DESIGN.md section 15 tabulates them (what fit_basis hands to the kernel)."""
+    Q = M + 3 * G + 1
+    init, lo, hi, fixed = np.zeros(Q), np.zeros(Q), np.zeros(Q), np.zeros(Q, bool)
+    init[:M] = np.nan if amplitude_start is None else np.asarray(amplitude_start, dtype=np.float64)
+    hi[:M] = np.inf
+    lo[M:M + G], hi[M:M + G] = -max_shift, max_shift
+    init[M + G:M + 2 * G], hi[M + G:M + 2 * G] = np.pi * broadening_start, np.pi * max_broadening
+    if lineshape == "voigt":
+        init[M + 2 * G:M + 3 * G] = gaussian_damping(gaussian_start)
+        hi[M + 2 * G:M + 3 * G] = gaussian_damping(max_gaussian)
+    else:
+        fixed[M + 2 * G:M + 3 * G] = True
+    lo[-1], hi[-1] = -np.inf, np.inf
+    fixed[-1] = not fit_phase
+    return init, lo, hi, fixed
+
+
+def make_basis(M, n, dt, seed):
+    """M multiplet FIDs [M, n] complex128: metabolite m has 1 ... 3 Lorentzian lines of its own around a centre spread
+    over 70 % of the spectral width, relative intensities summing to 1, natural damping 6 ... 14 /s."""
+    rng = np.random.default_rng([seed, M])
+    t = np.arange(n) * dt
+    sw = 1.0 / dt
+    centres = np.linspace(-0.35, 0.35, M) * sw if M > 1 else np.zeros(1)
+    B = np.zeros((M, n), dtype=np.complex128)
+    for m in range(M):
+        k = 1 + m % 3
+        w = rng.uniform(0.5, 1.5, k)
+        w /= w.sum()
+        step = 0.35 * sw / max(M, 4)
+        f = centres[m] + (np.arange(k) - (k - 1) / 2.0) * 0.25 * step + rng.uniform(-0.03, 0.03, k) * step
+        d = rng.uniform(6.0, 14.0, k)
+        B[m] = np.sum(w[:, None] * np.exp((-d[:, None] + 2j * np.pi * f[:, None]) * t), axis=0)
+    return B
+
+
+def kernel_case(M, G, n, seed, lineshape="voigt", fit_phase=True, skip=0, n_vox=2, dt=2.5e-4, noise=0.02,
+                amplitude_start=None, absent=()):
+    """Seeded case: basis, group = m mod G (so that the groups interleave), per-case truth inside the bounds (shift
+    +-4 Hz, Lorentzian 1 ... 5 Hz, Gaussian 1 ... 5 Hz for voigt, phase +-0.4 rad, amplitudes 0.5 ... 2; the
+    metabolites in `absent` have amplitude 0) and n_vox voxels that differ in their noise.  Returns a dict: x
+    [n_vox, n] complex128, B, group, dt, skip, truth [Q], init, lo, hi, fixed [Q], M, G."""
+    rng = np.random.default_rng([seed, M, G, n])
+    B = make_basis(M, n, dt, seed)
+    group = np.arange(M, dtype=np.int32) % G
+    init, lo, hi, fixed = parameters(M, G, lineshape, fit_phase=fit_phase, amplitude_start=amplitude_start)
+    truth = np.zeros(M + 3 * G + 1)
+    truth[:M] = rng.uniform(0.5, 2.0, M)
+    for m in absent:
+        truth[m] = 0.0
+    truth[M:M + G] = rng.uniform(-4.0, 4.0, G)
+    truth[M + G:M + 2 * G] = np.pi * rng.uniform(1.0, 5.0, G)
+    if lineshape == "voigt":
+        truth[M + 2 * G:M + 3 * G] = gaussian_damping(rng.uniform(1.0, 5.0, G))
+    truth[-1] = rng.uniform(-0.4, 0.4) if fit_phase else 0.0
+    z = rng.standard_normal((n_vox, n)) + 1j * rng.standard_normal((n_vox, n))
+    x = model(truth, B, group, dt)[None] + noise * z
+    return {"x": x, "B": B, "group": group, "dt": dt, "skip": skip, "truth": truth, "init": init, "lo": lo, "hi": hi,
+            "fixed": fixed, "M": M, "G": G}
+
+
+def step_cases():
+    """(name, kernel_case arguments) of the cases on which the first trial steps are compared one by one: both sides of
+    the 16-column tile, the largest fit, both lineshapes, a fixed phase, skipped points, ragged record lengths."""
+    return [
+        ("M1G1_n300", dict(M=1, G=1, n=300, seed=41)),
+        ("M3G3_lorentz_n1000", dict(M=3, G=3, n=1000, seed=42, lineshape="lorentzian")),
+        ("M12G2_skip5_n1500", dict(M=12, G=2, n=1500, seed=43, skip=5)),
+        ("M16G2_nophase_n2048", dict(M=16, G=2, n=2048, seed=44, fit_phase=False)),
+        ("M40G13_n2049", dict(M=40, G=13, n=2049, seed=45)),
+    ]

@@ -10,7 +10,7 @@ __version__ = "0.4.0"
 from . import _lib  # noqa: F401
 from .accessor import XmrisAccessor, register_xarray_accessor
 from .config import ATTRS, COORDS, DIMS
-from .fitting import fit_amares, simulate_fid
+from .fitting import basis_model, fit_amares, fit_basis, simulate_fid
 from .fused import spectral_pipeline
 from .labeled import Coordinate, LabeledArray
 from .vendor.bruker import remove_digital_filter
@@ -21,5 +21,5 @@ DataArray = LabeledArray  # convenience alias for code written against xarray's 
 register_xarray_accessor()  # no-op when xarray is absent or the name `xmr` is already owned
 
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "ATTRS", "COORDS", "DIMS", "Coordinate", "DataArray", "LabeledArray", "XmrisAccessor",
-           "apodize_exp", "apodize_lg", "autophase", "autophase_each", "fft", "fit_amares", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
+           "apodize_exp", "apodize_lg", "autophase", "autophase_each", "basis_model", "fft", "fit_amares", "fit_basis", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
            "phase", "register_xarray_accessor", "remove_digital_filter", "remove_water", "simulate_fid", "spectral_pipeline", "to_fid", "to_image", "to_kspace", "to_spectrum", "zero_fill"]

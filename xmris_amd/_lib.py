@@ -80,6 +80,10 @@ SIGNATURES = {
                            ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "xm_amares_fit_linked": (_i, [_p, _l, _l, _i, ctypes.c_double, ctypes.c_double, _i, _p, _p, _p, _p, _p, _p, _p, _i,
                                   ctypes.c_double, ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
+    "xm_basis_model": (_i, [_p, _l, _p, _i, _p, _i, _i, ctypes.c_double, _p, _p]),
+    "xm_basis_workspace_bytes": (_l, [_l, _i, _i]),
+    "xm_basis_fit": (_i, [_p, _l, _l, _i, ctypes.c_double, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, ctypes.c_double,
+                          ctypes.c_double, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "xm_coil_combine": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _p, _i, _i, _i, _p, _p]),
     "xm_align_workspace_bytes": (_l, [_l, _i, _l, _i]),
     "xm_align_rows": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _i, ctypes.c_double, ctypes.c_double,

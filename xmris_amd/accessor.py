@@ -152,6 +152,19 @@ class XmrisFittingMixin:
                           initialize_with_lm=initialize_with_lm, num_workers=num_workers, init_fid=init_fid,
                           verbose=verbose)
 
+    def fit_basis(self, basis, dim: str = "time", names=None, groups=None, lineshape: str = "voigt",
+                  max_shift: float = 10.0, max_broadening: float = 20.0, broadening_start: float = 2.0,
+                  max_gaussian: float = 20.0, gaussian_start: float = 2.0, fit_phase: bool = True, skip: int = 0,
+                  amplitude_start=None, max_iter: int = 200, return_fit: bool = True):
+        """Basis-set (linear-combination) quantification of every FID (an addition of this backend; DESIGN.md
+        section 15)."""
+        from .fitting.basis import fit_basis
+
+        return fit_basis(self._obj, basis, dim=dim, names=names, groups=groups, lineshape=lineshape,
+                         max_shift=max_shift, max_broadening=max_broadening, broadening_start=broadening_start,
+                         max_gaussian=max_gaussian, gaussian_start=gaussian_start, fit_phase=fit_phase, skip=skip,
+                         amplitude_start=amplitude_start, max_iter=max_iter, return_fit=return_fit)
+
 
 class XmrisAccessor(XmrisFourierMixin, XmrisProcessingMixin, XmrisPhasingMixin, XmrisVendorMixin, XmrisFusedMixin,
                     XmrisFittingMixin, XmrisMrsiMixin):

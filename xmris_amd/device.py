@@ -388,6 +388,93 @@ def amares_fit(x, axis: int, init, lo, hi, fixed, dt: float, t0: float = 0.0, ma
                      fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)
 
 
+def _basis_groups(group, m: int):
+    group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+    if group.size != m:
+        raise ValueError(f"group must name one group per metabolite ({m}), got {group.size}")
+    return group, (int(group.max()) + 1 if m else 0)
+
+
+def basis_model(params, basis, group, dt: float):
+    """Basis-set model: params [..., Q] fp64 device tensor (Q = M + 3 G + 1: amplitudes, then
+    shifts [Hz], Lorentzian dampings [1/s] and Gaussian dampings [1/s^2] per group, then the phase [rad]), basis [M, n]
+    complex device tensor, group [M] host indices -> complex128 FIDs [..., n] at t_j = j dt."""
+    torch = _torch()
+    _require_device(params)
+    _require_device(basis)
+    b = basis.to(torch.complex128).contiguous()
+    if b.dim() != 2:
+        raise ValueError(f"basis_model needs a basis [n_metab, n], got {tuple(b.shape)}")
+    m, n = b.shape
+    group, g = _basis_groups(group, m)
+    p = params.to(torch.float64).contiguous()
+    q = m + 3 * g + 1
+    if p.dim() < 1 or p.shape[-1] != q:
+        raise ValueError(f"basis_model needs parameters [..., {q}], got {tuple(p.shape)}")
+    lead = tuple(p.shape[:-1])
+    nb = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    out = torch.empty(lead + (n,), dtype=torch.complex128, device=p.device)
+    _lib.call("xm_basis_model", p.data_ptr(), nb, b.data_ptr(), m, group.ctypes.data, g, n, float(dt), out.data_ptr(),
+              _stream(p))
+    return out
+
+
+class BasisFit:
+    """Raw outputs of ``basis_fit`` with the non-time axes of the input in front: params [..., Q] (fitting units, the
+    layout of ``basis_model``), amp_sd [..., M] (not yet scaled by sigma), rss [...], status [...] (0 converged,
+    1 iteration cap, 2 non-finite), iters [...], fit [..., n] complex128 (or None); n_free: the free columns."""
+
+    __slots__ = ("params", "amp_sd", "rss", "status", "iters", "fit", "n_free")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def basis_fit(x, axis: int, basis, group, init, lo, hi, fixed, dt: float, skip: int = 0, max_iter: int = 200,
+              ftol: float = 1e-10, xtol: float = 1e-10, want_fit: bool = True) -> BasisFit:
+    """One Levenberg-Marquardt basis-set fit per FID along `axis` of the complex64 / complex128 device tensor `x`, all
+    voxels in one launch (xm_basis_fit).  basis: [M, n] complex device tensor on the data's time
+    grid; group [M]: host group indices; init / lo / hi / fixed: [Q] host arrays in the layout of ``basis_model``,
+    shared by every voxel (a NaN amplitude start: the automatic per-voxel start)."""
+    torch = _torch()
+    _require_device(x)
+    _require_device(basis)
+    code = _dtype_code(x)
+    axis = axis % x.dim()
+    x2, restore = _rows(x, axis)
+    nb, n = x2.shape
+    b = basis.to(torch.complex128).contiguous()
+    if b.dim() != 2 or b.shape[1] != n:
+        raise ValueError(f"basis_fit needs a basis [n_metab, {n}], got {tuple(b.shape)}")
+    m = b.shape[0]
+    group, g = _basis_groups(group, m)
+    q = m + 3 * g + 1
+    init, lo, hi = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (init, lo, hi))
+    fixed = np.ascontiguousarray(np.asarray(fixed, dtype=bool).reshape(-1).astype(np.int32))
+    if not (init.size == lo.size == hi.size == fixed.size == q):
+        raise ValueError(f"init, lo, hi and fixed must all hold {q} values")
+    lead = tuple(s for i, s in enumerate(x.shape) if i != axis)
+    dev_ = x.device
+    params = torch.empty((nb, q), dtype=torch.float64, device=dev_)
+    asd = torch.empty((nb, m), dtype=torch.float64, device=dev_)
+    rss = torch.empty(nb, dtype=torch.float64, device=dev_)
+    status = torch.empty(nb, dtype=torch.int32, device=dev_)
+    iters = torch.empty(nb, dtype=torch.int32, device=dev_)
+    fit = torch.empty((nb, n), dtype=torch.complex128, device=dev_) if want_fit else None
+    need = int(_lib.load().xm_basis_workspace_bytes(nb, n, m))
+    work = torch.zeros(max(need, 8), dtype=torch.uint8, device=dev_)
+    ptr = lambda a: a.ctypes.data  # noqa: E731  (host arrays)
+    _lib.call("xm_basis_fit", x2.data_ptr(), n, nb, n, float(dt), int(skip), b.data_ptr(), m, ptr(group), g, ptr(init),
+              ptr(lo), ptr(hi), ptr(fixed), int(max_iter), float(ftol), float(xtol), params.data_ptr(), asd.data_ptr(),
+              rss.data_ptr(), status.data_ptr(), iters.data_ptr(), fit.data_ptr() if fit is not None else None,
+              work.data_ptr(), need, code, _stream(x))
+    n_free = int(np.count_nonzero(~(fixed.astype(bool) | (lo == hi))))
+    return BasisFit(params=params.reshape(lead + (q,)), amp_sd=asd.reshape(lead + (m,)), rss=rss.reshape(lead),
+                    status=status.reshape(lead), iters=iters.reshape(lead),
+                    fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)
+
+
 class CoilCombine:
     """Raw outputs of ``coil_combine`` with the axes of the input other than coil and time in front, in the input's
     order: y [..., N] (the input's dtype), weights [..., C] complex128, quality [...] fp64, status [...] int32

@@ -1,7 +1,8 @@
-"""Quantification: AMARES time-domain fitting on the GPU (reference ``src/xmris/fitting``)."""
+"""Quantification: AMARES and basis-set time-domain fitting on the GPU (reference ``src/xmris/fitting``)."""
 from .amares import fit_amares
+from .basis import basis_model, fit_basis
 from .dataset import LabeledDataset
 from .prior_knowledge import PriorKnowledge, read_prior_knowledge
 from .simulation import simulate_fid
 
-__all__ = ["LabeledDataset", "PriorKnowledge", "fit_amares", "read_prior_knowledge", "simulate_fid"]
+__all__ = ["LabeledDataset", "PriorKnowledge", "basis_model", "fit_amares", "fit_basis", "read_prior_knowledge", "simulate_fid"]
