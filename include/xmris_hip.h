@@ -405,6 +405,30 @@ int xm_denoise_patches(const void* x, void* y, int32_t* rank_out, double* sigma,
 int xm_axis_dft(const void* x, void* y, const void* table, int64_t n_outer, int n, int m, int64_t n_inner, int dtype,
                 void* stream);
 
+/* ---- SENSE unfolding of regularly undersampled MRSI (this backend's own definition, the reference
+ * has none).  `a`: the aliased reduced-FOV images of C coils, n[0] x n[1] x n[2] voxels (an unused dim has n = accel = 1)
+ * and N_t time points; `a_strides`: element strides of its outer, coil and three spatial axes, `y_strides`: of the outer
+ * and three spatial axes of `y`, which holds N_d = accel[d] n[d] voxels per dim; time is contiguous and last in both.
+ * `sens`: [C, N_0, N_1, N_2] complex128, contiguous; `linv_or_null`: L^-1 of the noise covariance L L^H, C x C complex128
+ * row-major, or NULL for the identity.  The group of the reduced voxel p holds the R = accel[0] accel[1] accel[2] voxels
+ * q_d = (p_d - n[d] / 2 + N_d / 2 + k_d n[d]) mod N_d, member k = (k_0 accel[1] + k_1) accel[2] + k_2.  Its active members
+ * are those whose sensitivity is not zero in every coil; S = their C x Ra columns, Sw = Linv S, A = Sw^H Sw,
+ * lambda' = regularization trace(A) / Ra, B = (A + lambda' I)^-1 Sw^H by Cholesky, U = sqrt(R) B Linv;
+ * y[q_k, t] = sum_c U[k][c] a_c[p, t] in ascending c, every step a fused multiply-add in fp64, rounded once to `dtype`
+ * (XM_C64 / XM_C128); g[q_k] = sqrt((B B^H)_kk A_kk).  `g_or_null` (fp64) and `status_or_null` (int32): [n_outer, N_0,
+ * N_1, N_2], per full-FOV voxel: 0 unfolded; 1 a masked member (y zero, g 0), also every member of a group without an
+ * active one; 2 a non-finite sensitivity or data sample in the group, 3 a Cholesky pivot <= 0 or non-finite, and always Ra > C at regularization 0 (2 wins over 3): y zero and
+ * g NaN for every member of the group.  A group depends on its own samples only.  `workspace`:
+ * XM_SENSE_WORKSPACE_BYTES of device memory, zero on entry to the first call and left zero by every call.  Non-NULL
+ * pointers (g and status may be NULL), 1 <= C <= 64, accel >= 1, R <= 16, n >= 1, N_t >= 1, n_outer >= 0, at most
+ * 2^32 - 1 groups, a finite regularization >= 0, a known dtype and y != a: otherwise XM_ERR_INVALID_ARG before any HIP
+ * call.  n_outer = 0 launches nothing. */
+#define XM_SENSE_WORKSPACE_BYTES 256
+int xm_sense_unfold(const void* a, void* y, const void* sens, const void* linv_or_null, double* g_or_null,
+                    int32_t* status_or_null, int64_t n_outer, int C, const int32_t n[3], const int32_t accel[3], int N_t,
+                    const int64_t a_strides[5], const int64_t y_strides[4], double regularization, int dtype,
+                    void* workspace, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

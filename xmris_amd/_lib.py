@@ -42,6 +42,8 @@ XM_DENOISE_GRAM_FMA = 0x100
 XM_DENOISE_STOP_GRAM = 0x200
 XM_DENOISE_STOP_EIG = 0x400
 
+XM_SENSE_WORKSPACE_BYTES = 256
+
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
 XM_ERR_HIP = -3
@@ -92,6 +94,7 @@ SIGNATURES = {
                           ctypes.c_double, _i, _p, _p]),
     "xm_denoise_patches": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "xm_axis_dft": (_i, [_p, _p, _p, _l, _i, _i, _l, _i, _p]),
+    "xm_sense_unfold": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _i, _p, _p, ctypes.c_double, _i, _p, _p]),
     "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

@@ -141,6 +141,15 @@ class XmrisMrsiMixin:
 
         return to_kspace(self._obj, dim=dim, out_dim=out_dim, matrix=matrix, filter=filter, shift=shift)
 
+    def unfold_sense(self, sensitivities, accel, dims=(DIMS.x, DIMS.y), coil_dim: str = DIMS.coil,
+                     time_dim: str = DIMS.time, noise_cov=None, regularization: float = 0.0, return_maps: bool = False):
+        """SENSE unfolding of the aliased images of a regularly undersampled k-space, one launch for all voxel groups
+        (an addition of this backend)."""
+        from .processing.sense import unfold_sense
+
+        return unfold_sense(self._obj, sensitivities, accel, dims=dims, coil_dim=coil_dim, time_dim=time_dim,
+                            noise_cov=noise_cov, regularization=regularization, return_maps=return_maps)
+
 
 class XmrisFittingMixin:
     def fit_amares(self, prior_knowledge_file, dim: str = "time", mhz: float = None, sw: float = None,

@@ -67,6 +67,9 @@ class _Attrs(_Vocabulary):
     mrsi_matrix = XmrisTerm("mrsi_matrix", "Points along each transformed dimension after the reconstruction (the interpolated matrix).")
     mrsi_filter = XmrisTerm("mrsi_filter", "Spatial filter of the reconstruction: 'none', 'hamming', 'hann' or 'custom'.")
     mrsi_shift = XmrisTerm("mrsi_shift", "Shift applied along each transformed dimension.", "output points")
+    sense_dims = XmrisTerm("sense_dims", "Names of the undersampled dimensions the SENSE unfolding restored to the full field of view.")
+    sense_accel = XmrisTerm("sense_accel", "Acceleration along each unfolded dimension.")
+    sense_regularization = XmrisTerm("sense_regularization", "Tikhonov weight of the SENSE unfolding, relative to the mean diagonal of S^H Psi^-1 S.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 

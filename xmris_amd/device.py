@@ -11,6 +11,8 @@ kernels see ``[n_batch, n]`` C-contiguous rows, and moved back afterwards, exact
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from . import _lib
@@ -546,6 +548,97 @@ def coil_combine(x, coil_axis: int, time_axis: int, method: str = "svd", referen
               li.data_ptr() if li is not None else None, COIL_METHODS[method], int(n_points),
               int(code == _lib.XM_C128), work.data_ptr(), _stream(x))
     return CoilCombine(y=y, weights=w, quality=quality, status=status)
+
+
+class SenseUnfold:
+    """Raw outputs of ``unfold_sense``: y, the input without its coil axis and with the spatial axes grown to
+    N = accel n (the input's dtype, its axis order, time last); g fp64 and status int32 per full-FOV voxel, the batch
+    axes in front and the spatial axes in the order they were given (0 unfolded, 1 masked, 2 non-finite sample,
+    3 not positive definite)."""
+
+    __slots__ = ("y", "g", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+SENSE_MAX_COILS = 64
+SENSE_MAX_ACCEL = 16
+
+
+def unfold_sense(x, sens, coil_axis: int, spatial_axes, time_axis: int, accel, linv=None, regularization: float = 0.0,
+                 workspace=None) -> SenseUnfold:
+    """SENSE unfolding of the aliased complex64 / complex128 device tensor `x` in one launch (xm_sense_unfold, DESIGN.md
+    section 16).  `spatial_axes`: 1 ... 3 undersampled axes, `accel`: the acceleration along each; every axis but these,
+    `coil_axis` and `time_axis` is batch.  `sens`: [C, N...] complex, the spatial axes in the order of `spatial_axes`
+    (host values or a device tensor; uploaded as complex128).  `linv`: L^{-1} of the noise covariance L L^H, [C, C], or
+    None for the identity.  With time last the coil and spatial axes are addressed where they lie; a tensor whose time
+    axis is not contiguous, or whose batch axes do not fold into one stride, costs one contiguous copy.  `workspace`: a
+    zeroed uint8 tensor of XM_SENSE_WORKSPACE_BYTES to reuse between calls."""
+    torch = _torch()
+    _require_device(x)
+    nd = x.dim()
+    coil_axis, time_axis = coil_axis % nd, time_axis % nd
+    axes = [int(a) % nd for a in spatial_axes]
+    acc = [int(r) for r in accel]
+    if not 1 <= len(axes) <= 3 or len(acc) != len(axes):
+        raise ValueError(f"spatial_axes: needs 1 ... 3 axes and one accel per axis, got {len(axes)} and {len(acc)}")
+    if len({coil_axis, time_axis, *axes}) != len(axes) + 2:
+        raise ValueError("coil_axis, time_axis and spatial_axes must all differ")
+    if any(r < 1 for r in acc) or int(np.prod(acc)) > SENSE_MAX_ACCEL:
+        raise ValueError(f"accel: every entry must be >= 1 and their product at most {SENSE_MAX_ACCEL}, got {acc}")
+    c, nt = int(x.shape[coil_axis]), int(x.shape[time_axis])
+    small = [int(x.shape[a]) for a in axes]
+    full = [r * n for r, n in zip(acc, small)]
+    if not 1 <= c <= SENSE_MAX_COILS or nt < 1 or min(small) < 1:
+        raise ValueError(f"needs 1 ... {SENSE_MAX_COILS} coils and no empty axis, got shape {tuple(x.shape)}")
+    batch = [a for a in range(nd) if a not in (coil_axis, time_axis, *axes)]
+
+    def folds(v):  # the batch axes in front of v fold into one stride
+        return all(v.stride(i) == v.stride(i + 1) * v.shape[i + 1] for i in range(len(batch) - 1))
+
+    xv = x.permute(batch + [coil_axis] + axes + [time_axis])
+    if xv.numel() and (xv.stride(-1) != 1 and nt > 1 or not folds(xv)):
+        xv = xv.contiguous()
+    code = _dtype_code(xv)
+    dev_ = x.device
+    if isinstance(sens, torch.Tensor):
+        s = sens.to(device=dev_, dtype=torch.complex128).contiguous()
+    else:
+        s = torch.from_numpy(np.array(sens, dtype=np.complex128, order="C")).to(dev_)  # (a copy: the source may be read-only)
+    if tuple(s.shape) != (c, *full):
+        raise ValueError(f"sens must be {[c, *full]} (coils, then accel x size per spatial axis), got {list(s.shape)}")
+    li = None
+    if linv is not None:
+        li = torch.as_tensor(np.ascontiguousarray(linv, dtype=np.complex128) if not hasattr(linv, "detach") else linv)
+        li = li.to(dev_, torch.complex128).contiguous()
+        if tuple(li.shape) != (c, c):
+            raise ValueError(f"linv must be [{c}, {c}], got {tuple(li.shape)}")
+    # y: batch axes in front, then the spatial axes in the input's own order, then time
+    kept = sorted(axes)
+    bshape = [int(x.shape[a]) for a in batch]
+    yc = torch.empty(bshape + [full[axes.index(a)] for a in kept] + [nt], dtype=x.dtype, device=dev_)
+    nb = len(batch)
+    yv = yc.permute(list(range(nb)) + [nb + kept.index(a) for a in axes] + [nb + len(axes)])
+    g = torch.empty(bshape + full, dtype=torch.float64, device=dev_)
+    status = torch.empty(bshape + full, dtype=torch.int32, device=dev_)
+    pad = 3 - len(axes)
+    n_outer = int(np.prod(bshape, dtype=np.int64))
+    if n_outer > 0:
+        ostride = lambda v: int(v.stride(nb - 1)) if nb else 0  # noqa: E731
+        a_str = [ostride(xv), int(xv.stride(nb))] + [0] * pad + [int(xv.stride(nb + 1 + i)) for i in range(len(axes))]
+        y_str = [ostride(yv)] + [0] * pad + [int(yv.stride(nb + i)) for i in range(len(axes))]
+        i32, i64 = ctypes.c_int32 * 3, ctypes.c_int64
+        work = workspace if workspace is not None else torch.zeros(_lib.XM_SENSE_WORKSPACE_BYTES, dtype=torch.uint8, device=dev_)
+        _lib.call("xm_sense_unfold", xv.data_ptr(), yc.data_ptr(), s.data_ptr(), li.data_ptr() if li is not None else None,
+                  g.data_ptr(), status.data_ptr(), n_outer, c, i32(*([1] * pad + small)), i32(*([1] * pad + acc)), nt,
+                  (i64 * 5)(*a_str), (i64 * 4)(*y_str), float(regularization), code, work.data_ptr(), _stream(x))
+    # back to the input's axis order (without the coil axis, time last)
+    order = [a for a in range(nd) if a not in (coil_axis, time_axis)]
+    have = batch + kept
+    y = yc.permute([have.index(a) for a in order] + [len(have)])
+    return SenseUnfold(y=y if y.is_contiguous() else y.contiguous(), g=g, status=status)
 
 
 class AlignRows:

@@ -7,10 +7,11 @@ from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .mrsi import to_image, to_kspace
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
 from .phasing import autophase, autophase_each, phase
+from .sense import sense_maps, unfold_sense
 from .water import remove_water
 
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
-           "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace"]
+           "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled
