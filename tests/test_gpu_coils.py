@@ -260,6 +260,41 @@ def test_samples_whose_gram_matrix_overflows_are_reported():
             assert np.array_equal(got[k][good], clean[k]), (method, k)
 
 
+# ---- 8b. scale --------------------------------------------------------------------------------------------------------
+def _scaled(x, e):
+    if x.dtype == np.complex64:
+        return (x * np.float32(2.0 ** e)).astype(np.complex64)
+    return np.ldexp(x.real, e) + 1j * np.ldexp(x.imag, e)
+
+
+@pytest.mark.parametrize("dtype", ["complex128", "complex64"])
+def test_a_power_of_two_scale_changes_no_bit(dtype):
+    """Every operation is homogeneous, every threshold relative, and a power of two commutes with rounding: the weights,
+    the quality and the status of 2^k x have the bits of x's, y is exactly 2^k times x's."""
+    x, _ = _case("c8_n63_v37", dtype)
+    base = _run(x)
+    assert np.all(base["status"] == 0)
+    for e in (40, -40):
+        got = _run(_scaled(x, e))
+        for k in ("w", "quality", "status"):
+            assert np.array_equal(got[k], base[k]), (e, k)
+        assert np.array_equal(got["y"], _scaled(base["y"], e)), e
+
+
+def test_samples_at_the_ends_of_the_exponent_range():
+    """complex128.  x 2^-300: R R^H is 2^-600 times what it was, its square underflows to zero; the Jacobi stopping test
+    takes its norms on a scaled G, so the voxels are combined as their unscaled selves (status 0, weights and quality
+    within COIL_TOL of the unscaled run, y scaled).  x 2^300: the squared norm of R R^H overflows, the documented
+    status 2 with y and w zero and the quality NaN."""
+    x, want = _case("c8_n63_v37", "complex128")
+    base, got = _run(x), _run(_scaled(x, -300))
+    back = dict(got, y=_scaled(got["y"], 300))
+    print(f"2^-300: status {np.unique(got['status'])}, bits equal {_same(back, base)}")
+    _check(back, dict(want, y=base["y"], w=base["w"], quality=base["quality"]), what="x 2^-300 against x")
+    big = _run(_scaled(x, 300))
+    assert np.all(big["status"] == 2) and not big["y"].any() and not big["w"].any() and np.all(np.isnan(big["quality"]))
+
+
 # ---- 9. chaining ------------------------------------------------------------------------------------------------------
 def test_result_feeds_the_single_channel_chain():
     x = orc.make_data(5, 8, 1, 64, seed=81, snr=(20.0, 30.0))[:, :, 0, :]

@@ -94,6 +94,44 @@ def test_matrix_core_and_fma_gram_agree(name):
     _check(a, dict(b, lam=want["lam"]), x, what=f"{name} mfma against fma")
 
 
+# ---- 1b. scale ------------------------------------------------------------------------------------------------------------
+def _scaled(x, e):
+    if x.dtype == np.complex64:
+        return (x * np.float32(2.0 ** e)).astype(np.complex64)
+    if x.dtype == np.float64:
+        return np.ldexp(x, e)
+    return np.ldexp(x.real, e) + 1j * np.ldexp(x.imag, e)
+
+
+@pytest.mark.parametrize("dtype", ["complex128", "complex64"])
+def test_a_power_of_two_scale_changes_no_bit(dtype):
+    """Every operation is homogeneous, every threshold relative, and a power of two commutes with rounding: the rank and
+    the status of 2^k x have the bits of x's, y and sigma are exactly 2^k times x's."""
+    x, patch, _ = _case("g6x7_p3x3_n65", dtype)
+    base = _run(x, patch)
+    assert np.all(base["status"] == 0)
+    for e in (40, -40):
+        got = _run(_scaled(x, e), patch)
+        assert np.array_equal(got["rank"], base["rank"]) and np.array_equal(got["status"], base["status"]), e
+        assert np.array_equal(got["y"], _scaled(base["y"], e)), e
+        assert np.array_equal(got["sigma"], _scaled(base["sigma"], e)), e
+
+
+def test_samples_at_the_ends_of_the_exponent_range():
+    """complex128.  x 2^-300: G is 2^-600 times what it was, its square underflows to zero; the Jacobi stopping test
+    takes its norms on a scaled G, so the voxels are denoised as their unscaled selves (status 0, the rank equal, y and
+    sigma scaled and within the file's bounds of the unscaled run).  x 2^300: the squared norm of G overflows, the
+    documented status 2 with y zero, rank 0 and sigma NaN, as the oracle has it."""
+    x, patch, want = _case("g6x7_p3x3_n65", "complex128")
+    base, got = _run(x, patch), _run(_scaled(x, -300), patch)
+    back = dict(got, y=_scaled(got["y"], 300), sigma=_scaled(got["sigma"], 300))
+    print(f"2^-300: status {np.unique(got['status'])}, bits equal {all(np.array_equal(back[k], base[k]) for k in OUT)}")
+    _check(back, dict(want, y=base["y"], sigma=base["sigma"]), x, what="x 2^-300 against x")
+    big = _run(_scaled(x, 300), patch)
+    assert np.all(orc.denoise(_scaled(x, 300), patch)["status"] == 2)
+    assert np.all(big["status"] == 2) and not big["y"].any() and not big["rank"].any() and np.isnan(big["sigma"]).all()
+
+
 # ---- 2. bitwise properties ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["complex64", "complex128"])
 def test_a_voxel_does_not_depend_on_its_batch(dtype):

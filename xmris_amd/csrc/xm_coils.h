@@ -286,7 +286,9 @@ XM_DEV void cc_whiten(const CoilArgs& A, const CcLds& L) {
 // J = [[c, s e^{i phi}], [-s e^{-i phi}, c]], tau = (G_qq - G_pp) / (2 h), t = sign(tau) / (|tau| + sqrt(1 + tau^2)).
 // Every update is written as x - s (y + r x), y + s (x - r y) with r = s / (1 + c) (Rutishauser), and the pair's
 // diagonal as G_pp - t h, G_qq + t h, so that a small rotation leaves a small rounding error.  Returns the sweeps done,
-// XM_CC_SWEEPS + 1 when the off-diagonal norm never fell to eps ||G||_F, -1 when ||G||_F^2 is not finite.
+// XM_CC_SWEEPS + 1 when the off-diagonal norm never fell to eps ||G||_F, -1 when ||G||_F^2 is not finite.  Both
+// norms are taken on G times the power of two that brings its largest diagonal entry to [1, 2), so the squares of small
+// samples do not underflow to a test that is met at once (a G that is itself subnormal or zero is not helped by it).
 #define XM_CC_ROT 8  // doubles per rotation: c, s, cos phi, sin phi, r, new G_pp, new G_qq
 XM_DEV int cc_jacobi(const CcLds& L, int C) {
   const int t = threadIdx.x, np = (C + 1) / 2, players = 2 * np;
@@ -295,16 +297,26 @@ XM_DEV int cc_jacobi(const CcLds& L, int C) {
     Vm[2 * e] = (e / C == e % C) ? 1.0 : 0.0;
     Vm[2 * e + 1] = 0.0;
   }
+  double gmax = 0.0;  // (every thread alike: G is complete since cc_mirror's barrier)
+  for (int i = 0; i < C; ++i) gmax = fmax(gmax, fabs(L.G[2 * (i * C + i)]));
+  const int ex = gmax > 0.0 && isfinite(gmax) ? -ilogb(gmax) : 0;  // both norms on 2^ex G: exact, and no square underflows
   double f = 0.0;
-  for (int e = t; e < 2 * C * C; e += XM_CC_NT) f += L.G[e] * L.G[e];
+  for (int e = t; e < 2 * C * C; e += XM_CC_NT) {
+    const double g = ldexp(L.G[e], ex);
+    f += g * g;
+  }
   const double fro2 = cc_sum(L, f);  // (also the barrier after V's initialisation)
-  if (!isfinite(fro2)) return -1;    // samples so large that G or its norm overflows: nothing to iterate on
+  // samples so large that G or its norm overflows: nothing to iterate on
+  if (!isfinite(fro2) || !isfinite(ldexp(fro2, -2 * ex))) return -1;
   const double eps = 2.220446049250313e-16;
   int* pq = (int*)(L.rot + XM_CC_ROT * 32);  // pairs of the step, after the 32 rotations
   for (int sweep = 0;; ++sweep) {
     double o = 0.0;
     for (int e = t; e < C * C; e += XM_CC_NT)
-      if (e / C != e % C) o += L.G[2 * e] * L.G[2 * e] + L.G[2 * e + 1] * L.G[2 * e + 1];
+      if (e / C != e % C) {
+        const double gr = ldexp(L.G[2 * e], ex), gi = ldexp(L.G[2 * e + 1], ex);
+        o += gr * gr + gi * gi;
+      }
     const double off2 = cc_sum(L, o);
     if (!(off2 > eps * eps * fro2)) return sweep;
     if (sweep == XM_CC_SWEEPS) return XM_CC_SWEEPS + 1;

@@ -312,7 +312,8 @@ XM_DEV void hs_gram_mfma(const HsvdArgs& A, const HsLds& L, long long xoff, int&
 }
 
 // cc_jacobi (xm_coils.h) on G, eigenvectors in V: the sweeps done, XM_HS_SWEEPS + 1 at the cap, -1 when ||G||_F^2 is
-// not finite
+// not finite.  The norms of the stopping test are taken on G times a power of two, so small samples' squares do not
+// underflow to a test that is met at once; samples so small that G itself is subnormal or zero are not helped by it.
 XM_DEV int hs_jacobi(const HsLds& L, int C) {
   const int t = threadIdx.x, np = (C + 1) / 2, players = 2 * np;
   double* Vm = L.V;
@@ -320,16 +321,25 @@ XM_DEV int hs_jacobi(const HsLds& L, int C) {
     Vm[2 * e] = (e / C == e % C) ? 1.0 : 0.0;
     Vm[2 * e + 1] = 0.0;
   }
+  double gmax = 0.0;  // (every thread alike: G is complete since hs_mirror's barrier)
+  for (int i = 0; i < C; ++i) gmax = fmax(gmax, fabs(L.G[2 * (i * C + i)]));
+  const int ex = gmax > 0.0 && isfinite(gmax) ? -ilogb(gmax) : 0;  // both norms on 2^ex G: exact, and no square underflows
   double f = 0.0;
-  for (int e = t; e < 2 * C * C; e += XM_HS_NT) f += L.G[e] * L.G[e];
+  for (int e = t; e < 2 * C * C; e += XM_HS_NT) {
+    const double g = ldexp(L.G[e], ex);
+    f += g * g;
+  }
   const double fro2 = hs_sum(L, f);  // (also the barrier after V's initialisation)
-  if (!isfinite(fro2)) return -1;
+  if (!isfinite(fro2) || !isfinite(ldexp(fro2, -2 * ex))) return -1;  // G, or ||G||_F^2 itself, not finite
   const double eps = 2.220446049250313e-16;
   int* pq = (int*)(L.rot + XM_HS_ROT * 32);  // pairs of the step, after the 32 rotations
   for (int sweep = 0;; ++sweep) {
     double o = 0.0;
     for (int e = t; e < C * C; e += XM_HS_NT)
-      if (e / C != e % C) o += L.G[2 * e] * L.G[2 * e] + L.G[2 * e + 1] * L.G[2 * e + 1];
+      if (e / C != e % C) {
+        const double gr = ldexp(L.G[2 * e], ex), gi = ldexp(L.G[2 * e + 1], ex);
+        o += gr * gr + gi * gi;
+      }
     const double off2 = hs_sum(L, o);
     if (!(off2 > eps * eps * fro2)) return sweep;
     if (sweep == XM_HS_SWEEPS) return XM_HS_SWEEPS + 1;
