@@ -429,6 +429,21 @@ int xm_sense_unfold(const void* a, void* y, const void* sens, const void* linv_o
                     const int64_t a_strides[5], const int64_t y_strides[4], double regularization, int dtype,
                     void* workspace, void* stream);
 
+/* ---- Non-Cartesian gridding: a sparse real matrix along one axis (this backend's own definition,
+ * the reference has none).  x is viewed as (n_outer, n, n_inner) and y as (n_outer, n_rows, n_inner), both C-contiguous:
+ * any axis of a contiguous tensor is such a view, so nothing is transposed.  The matrix is in CSR form in device memory:
+ * `rowptr` (n_rows + 1 int32, ascending from 0), `col` (rowptr[n_rows] int32, each in [0, n)) and `val` (as many fp64).
+ *   y[o][r][i] = sum_{e = rowptr[r]}^{rowptr[r+1]-1} val[e] x[o][col[e]][i],
+ * the products and the sum in fp64 (ascending e, every step a fused multiply-add), rounded once to `dtype` (XM_C64 /
+ * XM_C128); a row without entries is written as zero.  No atomics: an output is one wave's sum in one fixed order and
+ * depends on its own entries only, so results are bitwise reproducible and independent of the batch.  The kernel trusts
+ * the table: the caller has checked it (xmris_amd.device.SparseTable does so on the host; a column out of range would
+ * read out of bounds); the entry count is bounded by rowptr's int32.  1 <= n, n_rows < 2^31, n_outer, n_inner >= 0, at
+ * most 2^50 elements in x or y, non-NULL pointers aligned to the element size, y != x and a known dtype: otherwise
+ * XM_ERR_INVALID_ARG before any HIP call.  n_outer = 0 or n_inner = 0 launches nothing. */
+int xm_axis_sparse(const void* x, void* y, const int32_t* rowptr, const int32_t* col, const double* val, int64_t n_outer,
+                   int64_t n, int64_t n_rows, int64_t n_inner, int dtype, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -70,6 +70,12 @@ class _Attrs(_Vocabulary):
     sense_dims = XmrisTerm("sense_dims", "Names of the undersampled dimensions the SENSE unfolding restored to the full field of view.")
     sense_accel = XmrisTerm("sense_accel", "Acceleration along each unfolded dimension.")
     sense_regularization = XmrisTerm("sense_regularization", "Tikhonov weight of the SENSE unfolding, relative to the mean diagonal of S^H Psi^-1 S.")
+    grid_dims = XmrisTerm("grid_dims", "Names of the dimensions that gridding put in place of the sample dimension.")
+    grid_matrix = XmrisTerm("grid_matrix", "Target matrix along each gridded dimension.")
+    grid_oversampled = XmrisTerm("grid_oversampled", "Points of the oversampled Cartesian grid along each gridded dimension.")
+    grid_width = XmrisTerm("grid_width", "Width of the Kaiser-Bessel gridding kernel.", "grid cells")
+    grid_beta = XmrisTerm("grid_beta", "Shape parameter of the Kaiser-Bessel gridding kernel along each gridded dimension.")
+    grid_density = XmrisTerm("grid_density", "Density compensation of the gridding: 'none', 'pipe' or 'custom'.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 
@@ -81,6 +87,7 @@ class _Dims(_Vocabulary):
     average = XmrisTerm("average", "Signal averages.")
     coil = XmrisTerm("coil", "Receive coils.")
     echo = XmrisTerm("echo", "Echoes.")
+    sample = XmrisTerm("sample", "Samples of a non-Cartesian k-space trajectory.")
     kx = XmrisTerm("kx", "k-space axis x.")
     ky = XmrisTerm("ky", "k-space axis y.")
     kz = XmrisTerm("kz", "k-space axis z.")

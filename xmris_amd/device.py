@@ -898,6 +898,92 @@ def axis_dft(x, axis: int, table):
     return out
 
 
+class SparseTable:
+    """A real sparse matrix [n_rows, n] in CSR form, checked on the host: the only form `axis_sparse` takes, because the
+    kernel trusts its table and a column out of range would read out of bounds on the GPU.  `rowptr` must ascend from 0
+    to ``len(col)``, every `col` must lie in [0, n) and every `val` must be finite (ValueError otherwise).  The arrays
+    are copied and frozen; the device copies are made once per device and kept with the object."""
+
+    __slots__ = ("rowptr", "col", "val", "n", "n_rows", "_device")
+
+    def __init__(self, rowptr, col, val, n: int):
+        rp, c, v = np.asarray(rowptr), np.asarray(col), np.asarray(val)
+        if rp.ndim != 1 or c.ndim != 1 or v.ndim != 1 or rp.dtype.kind not in "iu" or c.dtype.kind not in "iu":
+            raise ValueError("SparseTable: rowptr and col must be one-dimensional integer arrays, val one-dimensional")
+        if v.dtype.kind not in "fiu":
+            raise ValueError(f"SparseTable: val must be real, got {v.dtype}")
+        n = int(n)
+        if len(rp) < 2 or not 1 <= n < 2 ** 31 or len(rp) - 1 >= 2 ** 31 or len(c) >= 2 ** 31:
+            raise ValueError("SparseTable: needs 1 <= n, n_rows < 2^31 and fewer than 2^31 entries")
+        if len(v) != len(c):
+            raise ValueError(f"SparseTable: {len(c)} col for {len(v)} val")
+        rp = rp.astype(np.int64)
+        if rp[0] != 0 or rp[-1] != len(c) or np.any(np.diff(rp) < 0):
+            raise ValueError("SparseTable: rowptr must ascend from 0 to len(col)")
+        if len(c) and (c.min() < 0 or c.max() >= n):
+            bad = int(np.flatnonzero((c < 0) | (c >= n))[0])
+            raise ValueError(f"SparseTable: col[{bad}] = {int(c[bad])} is outside [0, {n})")
+        v = v.astype(np.float64)
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"SparseTable: val[{int(np.flatnonzero(~np.isfinite(v))[0])}] is not finite")
+        self.rowptr, self.col, self.val = rp.astype(np.int32), c.astype(np.int32), v
+        for a in (self.rowptr, self.col, self.val):
+            a.setflags(write=False)
+        self.n, self.n_rows = n, len(rp) - 1
+        self._device = {}
+
+    @property
+    def nnz(self) -> int:
+        return len(self.col)
+
+    def __setattr__(self, name, value):
+        if hasattr(self, "_device"):
+            raise AttributeError("SparseTable is immutable")
+        object.__setattr__(self, name, value)
+
+    def _on(self, device):
+        """(rowptr, col, val) tensors on `device`, uploaded on first use.  A table without entries still gets one
+        element per array: the library takes no null pointer."""
+        torch = _torch()
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = tuple(torch.from_numpy(a.copy() if len(a) else np.zeros(1, a.dtype)).to(device)
+                                      for a in (self.rowptr, self.col, self.val))
+        return self._device[key]
+
+
+def axis_sparse(x, axis: int, table: SparseTable):
+    """``y = table @ x`` along `axis` of the complex64 / complex128 device tensor `x` in one launch (xm_axis_sparse,
+    DESIGN.md section 17): `table` is a `SparseTable` [n_rows, n] with n the size of `axis` -- nothing else is taken,
+    the object is what has checked the indices.  Each output is the fp64 sum of its row's entries in their stored
+    order, rounded once to x's dtype; a row without entries gives zero.  Any axis of a contiguous tensor is read where it
+    lies; a tensor that is not contiguous costs one contiguous copy.  Returns a new tensor with n_rows points along
+    `axis`; `x` is left untouched."""
+    if not isinstance(table, SparseTable):
+        raise TypeError(f"axis_sparse takes its table as a SparseTable only, got {type(table).__name__}")
+    _require_device(x)
+    torch = _torch()
+    code = _dtype_code(x)
+    nd = x.dim()
+    if nd == 0:
+        raise ValueError("axis_sparse needs at least one axis")
+    axis = axis % nd
+    n = x.shape[axis]
+    if n != table.n:
+        raise ValueError(f"table is bound to an axis of {table.n} points, the axis has {n}")
+    xc = x if x.is_contiguous() else x.contiguous()
+    shape = tuple(xc.shape)
+    n_outer = int(np.prod(shape[:axis], dtype=np.int64))
+    n_inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    out = torch.empty(shape[:axis] + (table.n_rows,) + shape[axis + 1:], dtype=x.dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    rowptr, col, val = table._on(x.device)
+    _lib.call("xm_axis_sparse", xc.data_ptr(), out.data_ptr(), rowptr.data_ptr(), col.data_ptr(), val.data_ptr(),
+              n_outer, int(n), table.n_rows, n_inner, code, _stream(x))
+    return out
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 
