@@ -313,7 +313,7 @@ def truth_gap(res, x, z, a, k0, y):
                 sig=float(np.abs(res["y"] - y).max() / np.abs(x).max()))
 
 
-# ---- the kernel's pole iteration restated (xm_hsvd.h: hs_jacobi, hs_select, hs_shift_matrix, hs_hessenberg, hs_qr) -------
+# ---- the kernel's pole iteration restated (xm_wg.h: wg_jacobi; xm_hsvd.h: hs_select, hs_shift_matrix, hs_hessenberg, hs_qr) -------
 def jacobi_w(x, n_cols, rank, sweeps=30):
     """W (M x K) as the kernel forms it: cyclic Jacobi in the kernel's round-robin order on sum_l h_l h_l^H, a pair with
     G_pq = 0 skipped (so exact zeros stay exact), then the eigenvectors of the K largest diagonal entries, the largest

@@ -17,9 +17,10 @@
 // Every sum over time is taken the same way: thread t adds its points t, t + 256, ... in ascending order, a tree over
 // the 64 lanes of each wave, then the four waves in ascending order.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_AL_NT 256
+static_assert(XM_AL_NT == XM_WG_NT, "k_align runs xm_wg.h's workgroup");
 #define XM_AL_MAXL 8192     // points of z staged in the LDS (128 KiB as fp64)
 #define XM_AL_MAXGRID 1025  // coarse grid points 2 G + 1
 #define XM_AL_K 8           // grid indices g per coarse round; with -g: 16 frequencies, 32 sums per reduction
@@ -363,10 +364,7 @@ __global__ __launch_bounds__(XM_AL_NT) void k_align(AlignArgs A) {
   L.sum = (double2*)(L.out + XM_AL_RED + 2);
 
   for (;;) {
-    if (t == 0) *next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long w = (long long)*next;
-    __syncthreads();
+    const long long w = wg_next_item(A.counter, next);
     if (w >= A.nwork) break;
     if (!AVERAGE) {
       // w = (o A + a) n_inner + i
@@ -442,12 +440,5 @@ __global__ __launch_bounds__(XM_AL_NT) void k_align(AlignArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

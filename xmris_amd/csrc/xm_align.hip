@@ -11,15 +11,8 @@ XmResidency g_al_res[2];  // one residency record per kernel instantiation
 
 template <bool AVERAGE>
 int al_launch(const AlignArgs& A, hipStream_t st) {
-  const size_t lds = al_lds_bytes(A.L, A.G, A.R);
-  int resident = 0;
-  const int rc = xm_resident_blocks(g_al_res[AVERAGE], k_align<AVERAGE>, XM_AL_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = A.nwork < resident ? A.nwork : resident;
-  xm_note_kernel("k_align", nullptr, AVERAGE ? "average" : "each", A.L, A.G);  // <form, L, G>
-  hipLaunchKernelGGL(k_align<AVERAGE>, dim3((unsigned)blocks), dim3(XM_AL_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(g_al_res[AVERAGE], k_align<AVERAGE>, XM_AL_NT, al_lds_bytes(A.L, A.G, A.R), A.nwork, A, st,
+                         "k_align", AVERAGE ? "average" : "each", A.L, A.G);  // <form, L, G>
 }
 }  // namespace
 
@@ -87,6 +80,5 @@ extern "C" int xm_align_rows(const void* x, const void* r, int64_t r_voxel_strid
 
   DeviceGuard guard(x);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   return mean_or_null ? al_launch<true>(P, st) : al_launch<false>(P, st);
 }

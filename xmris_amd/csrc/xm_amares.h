@@ -18,16 +18,14 @@
 // ascending, then c ascending -- the order the oracle (tests/_amares_links.py) uses too.  k_amares_fit<false> is the
 // kernel without links: it never reads lk / sc / off and every column has one contribution.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_AM_MAXK 16                  // peaks
 #define XM_AM_MAXQ (5 * XM_AM_MAXK)    // physical parameters
 #define XM_AM_NT 256                   // threads per workgroup
 #define XM_AM_MAXE 13                  // accumulator entries per thread: ceil(((80+1)(80+2)/2 - 1) / 256)
 #define XM_AM_STAGE_BYTES 65536        // LDS budget of the staged [J | r] rows
-
-// bound types (lmfit's transforms)
-enum { XM_AM_FIXED = 0, XM_AM_FREE = 1, XM_AM_LO = 2, XM_AM_HI = 3, XM_AM_TWO = 4 };
+static_assert(XM_AM_NT == XM_WG_NT, "k_amares_fit runs xm_wg.h's workgroup");
 
 struct AmaresFitArgs {
   const void* x;       // rows of n complex samples (complex64 or complex128), `stride` elements apart
@@ -46,7 +44,7 @@ struct AmaresFitArgs {
   unsigned* counter;   // [2] zero at launch: row ticket, workgroups done
   double u0[XM_AM_MAXQ];  // free: internal start value; fixed: the physical value
   double lo[XM_AM_MAXQ], hi[XM_AM_MAXQ];
-  signed char bt[XM_AM_MAXQ];   // XM_AM_* bound type
+  signed char bt[XM_AM_MAXQ];   // XM_WG_* bound type (xm_wg.h)
   signed char col[XM_AM_MAXQ];  // free column of parameter q, -1 when fixed
   signed char lk[XM_AM_MAXQ];   // 1: q follows the root that owns col[q] (free roots only)
   double sc[XM_AM_MAXQ], off[XM_AM_MAXQ];  // p_q = sc * p_root + off where lk[q]; 1 and 0 elsewhere
@@ -60,28 +58,6 @@ XM_DEV void am_term(const double* p, double t, double& tr, double& ti) {
   sincos(p[3] + 2.0 * M_PI * p[1] * t, &s, &c);
   tr = e * c;
   ti = e * s;
-}
-
-// physical value and dp/du of a parameter from its internal value (lmfit's transforms).  A two-sided parameter at
-// sin u = +-1 (on a bound) has slope exactly 0: it stays where it is.
-XM_DEV void am_from_internal(int bt, double u, double lo, double hi, double& p, double& s) {
-  if (bt == XM_AM_TWO) {
-    double sn, cs;
-    sincos(u, &sn, &cs);
-    p = lo + (sn + 1.0) * (hi - lo) * 0.5;
-    s = (sn == 1.0 || sn == -1.0) ? 0.0 : cs * (hi - lo) * 0.5;
-  } else if (bt == XM_AM_LO) {
-    const double r = sqrt(u * u + 1.0);
-    p = lo - 1.0 + r;
-    s = u / r;
-  } else if (bt == XM_AM_HI) {
-    const double r = sqrt(u * u + 1.0);
-    p = hi + 1.0 - r;
-    s = -u / r;
-  } else {
-    p = u;
-    s = 1.0;
-  }
 }
 
 __global__ void k_amares_model(const double* __restrict__ params, long long nb, int K, int n, double dt, double t0,
@@ -130,7 +106,7 @@ XM_DEV void am_set_params(const AmaresFitArgs& A, const AmLds& L, const double* 
   if (t < 5 * A.K) {
     const int j = A.col[t];
     double p = A.u0[t], s = 0.0;
-    if (j >= 0) am_from_internal(A.bt[t], u[j], A.lo[t], A.hi[t], p, s);
+    if (j >= 0) wg_from_internal(A.bt[t], u[j], A.lo[t], A.hi[t], p, s);
     if (LINKED && A.lk[t]) {
       p = A.sc[t] * p + A.off[t];
       s = A.sc[t] * s;
@@ -163,15 +139,7 @@ XM_DEV double am_cost(const AmaresFitArgs& A, const AmLds& L, long long row, dou
       fit[2 * (long long)i + 1] = mi;
     }
   }
-  L.red[t] = c;
-  __syncthreads();
-  for (int h = XM_AM_NT / 2; h > 0; h >>= 1) {
-    if (t < h) L.red[t] += L.red[t + h];
-    __syncthreads();
-  }
-  const double r = L.red[0];
-  __syncthreads();
-  return r;
+  return wg_sum(L.red, c);
 }
 
 // factor of parameter q in the physical Jacobian: its link scale (1 for an unlinked parameter, which is exact)
@@ -297,53 +265,6 @@ XM_DEV void am_normal(const AmaresFitArgs& A, const AmLds& L, long long row, boo
   __syncthreads();
 }
 
-// Marquardt scale of a column: its largest squared norm so far, 1 for a column that has always been zero (MINPACK)
-XM_DEV double am_scale(double d) { return d > 0.0 ? d : 1.0; }
-
-// Cholesky factor of H + lam diag(dsc) (upper triangle of H and hd; lam = 0: H itself) into the lower triangle of H and
-// ld.  Column by column, rows spread over the workgroup.  false (every thread alike) when not positive definite.
-XM_DEV bool am_cholesky(const AmaresFitArgs& A, const AmLds& L, double lam) {
-  const int t = threadIdx.x, P = A.P;
-  for (int j = 0; j < P; ++j) {
-    double s = L.hd[j] + lam * am_scale(L.dsc[j]);
-    for (int k = 0; k < j; ++k) s -= L.H[j * P + k] * L.H[j * P + k];
-    if (!(s > 0.0) || !isfinite(s)) {
-      __syncthreads();
-      return false;
-    }
-    const double dj = sqrt(s);
-    for (int i = j + 1 + t; i < P; i += XM_AM_NT) {
-      double v = L.H[j * P + i];
-      for (int k = 0; k < j; ++k) v -= L.H[i * P + k] * L.H[j * P + k];
-      L.H[i * P + j] = v / dj;
-    }
-    if (t == 0) L.ld[j] = dj;
-    __syncthreads();
-  }
-  return true;
-}
-
-// dl <- (L L^T)^{-1} g; true when every component is finite
-XM_DEV bool am_solve(const AmaresFitArgs& A, const AmLds& L) {
-  const int P = A.P;
-  if (threadIdx.x == 0) {
-    for (int j = 0; j < P; ++j) {
-      double v = L.g[j];
-      for (int k = 0; k < j; ++k) v -= L.H[j * P + k] * L.dl[k];
-      L.dl[j] = v / L.ld[j];
-    }
-    for (int j = P - 1; j >= 0; --j) {
-      double v = L.dl[j];
-      for (int k = j + 1; k < P; ++k) v -= L.H[k * P + j] * L.dl[k];
-      L.dl[j] = v / L.ld[j];
-    }
-  }
-  __syncthreads();
-  bool ok = true;
-  for (int j = 0; j < P; ++j) ok = ok && isfinite(L.dl[j]);
-  return ok;
-}
-
 template <bool LINKED>
 __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
   extern __shared__ double am_sm[];
@@ -364,10 +285,7 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
   __shared__ unsigned next;
 
   for (;;) {
-    if (t == 0) next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long row = (long long)next;
-    __syncthreads();
+    const long long row = wg_next_item(A.counter, &next);
     if (row >= A.nb) break;
 
     // start: every voxel from the prior knowledge
@@ -390,8 +308,8 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
         need_jac = false;
       }
       ++it;
-      bool ok = am_cholesky(A, L, lam);
-      if (ok) ok = am_solve(A, L);
+      bool ok = wg_cholesky(L.H, L.hd, L.dsc, L.ld, P, lam);
+      if (ok) ok = wg_solve(L.H, L.ld, L.g, L.dl, P);
       if (!ok) {
         lam *= nu;
         nu *= 2.0;
@@ -400,7 +318,7 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
       }
       double dn = 0.0, un = 0.0, pred = 0.0;
       for (int j = 0; j < P; ++j) {
-        const double dj = am_scale(L.dsc[j]);
+        const double dj = wg_lm_scale(L.dsc[j]);
         const double sd = sqrt(dj) * L.dl[j], su = sqrt(dj) * L.u[j];
         dn += sd * sd;
         un += su * su;
@@ -439,7 +357,7 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
       // CRLB: sigma^2 (J^T J)^{-1} with J over the physical free columns at the solution; the caller scales.  A linked
       // amplitude's variance is sc^2 times its column's.
       am_normal<LINKED>(A, L, row, true);
-      const bool ok = am_cholesky(A, L, 0.0);
+      const bool ok = wg_cholesky(L.H, L.hd, L.dsc, L.ld, P, 0.0);
       if (t < K) {
         const int j = A.col[5 * t];
         double var = 0.0;
@@ -476,12 +394,5 @@ __global__ __launch_bounds__(XM_AM_NT) void k_amares_fit(AmaresFitArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

@@ -113,7 +113,7 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
     A.hi[q] = hi;
     if (fixed[q] || lo == hi) {
       if (!std::isfinite(v)) return am_fail("parameter " + std::to_string(q) + ": a fixed value must be finite");
-      A.bt[q] = XM_AM_FIXED;
+      A.bt[q] = XM_WG_FIXED;
       A.col[q] = -1;
       A.u0[q] = v;
       continue;
@@ -121,16 +121,16 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
     A.col[q] = (signed char)P++;
     const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
     if (fl && fh) {
-      A.bt[q] = XM_AM_TWO;
+      A.bt[q] = XM_WG_TWO;
       A.u0[q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
     } else if (fl) {
-      A.bt[q] = XM_AM_LO;
+      A.bt[q] = XM_WG_LO;
       A.u0[q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
     } else if (fh) {
-      A.bt[q] = XM_AM_HI;
+      A.bt[q] = XM_WG_HI;
       A.u0[q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
     } else {
-      A.bt[q] = XM_AM_FREE;
+      A.bt[q] = XM_WG_FREE;
       A.u0[q] = v;
     }
   }
@@ -172,20 +172,10 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
 
   DeviceGuard guard(in);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   const size_t lds = am_lds_bytes(P, A.lda, A.q_pts);
-  int resident = 0;
-  const int rc = any_link ? xm_resident_blocks(g_am_res_linked, k_amares_fit<true>, XM_AM_NT, lds, &resident, st)
-                          : xm_resident_blocks(g_am_res, k_amares_fit<false>, XM_AM_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = n_batch < resident ? n_batch : resident;
-  xm_note_kernel("k_amares_fit", nullptr, any_link ? "true" : "false", P, -1);  // <LINKED, free columns>
-  if (any_link)
-    hipLaunchKernelGGL(k_amares_fit<true>, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
-  else
-    hipLaunchKernelGGL(k_amares_fit<false>, dim3((unsigned)blocks), dim3(XM_AM_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  if (any_link)  // <LINKED, free columns>
+    return xm_launch_items(g_am_res_linked, k_amares_fit<true>, XM_AM_NT, lds, n_batch, A, st, "k_amares_fit", "true", P, -1);
+  return xm_launch_items(g_am_res, k_amares_fit<false>, XM_AM_NT, lds, n_batch, A, st, "k_amares_fit", "false", P, -1);
 }
 
 }  // extern "C"

@@ -18,16 +18,14 @@
 // (i 2 pi t T_g, -t T_g, -t^2 T_g).  x^ = sum_g T_g (groups ascending) and the phi column is i x^.  Every column is
 // chained through dp/du.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_BS_MAXQ 128                 // physical parameters M + 3 G + 1
 #define XM_BS_MAXP 80                  // free columns
 #define XM_BS_NT 256                   // threads per workgroup
 #define XM_BS_MAXE 13                  // accumulator entries per thread: ceil(((80+1)(80+2)/2 - 1) / 256)
 #define XM_BS_STAGE_BYTES 65536        // LDS budget of the staged [J | r] rows
-
-// bound types (lmfit's transforms)
-enum { XM_BS_FIXED = 0, XM_BS_FREE = 1, XM_BS_LO = 2, XM_BS_HI = 3, XM_BS_TWO = 4 };
+static_assert(XM_BS_NT == XM_WG_NT, "k_basis_fit and k_basis_norms run xm_wg.h's workgroup");
 
 struct BasisFitArgs {
   const void* x;        // rows of n complex samples (complex64 or complex128), `stride` elements apart
@@ -48,7 +46,7 @@ struct BasisFitArgs {
   unsigned* counter;   // [2] zero at launch: row ticket, workgroups done
   double u0[XM_BS_MAXQ];  // free: internal start value (NaN: an amplitude's automatic start); fixed: the physical value
   double lo[XM_BS_MAXQ], hi[XM_BS_MAXQ];
-  signed char bt[XM_BS_MAXQ];       // XM_BS_* bound type
+  signed char bt[XM_BS_MAXQ];       // XM_WG_* bound type (xm_wg.h)
   signed char col[XM_BS_MAXQ];      // free column of parameter q, -1 when fixed
   unsigned char ord[XM_BS_MAXQ];    // metabolites sorted by group, ascending m within a group
   unsigned char gs[XM_BS_MAXQ + 1]; // group g owns ord[gs[g] ... gs[g + 1])
@@ -120,44 +118,8 @@ __global__ __launch_bounds__(XM_BS_NT) void k_basis_norms(const double* __restri
     const double* b = basis + 2 * ((size_t)m * n + i);
     c += b[0] * b[0] + b[1] * b[1];
   }
-  red[t] = c;
-  __syncthreads();
-  for (int h = XM_BS_NT / 2; h > 0; h >>= 1) {
-    if (t < h) red[t] += red[t + h];
-    __syncthreads();
-  }
-  if (t == 0) bnorm[m] = sqrt(red[0]);
-}
-
-// physical value and dp/du of a parameter from its internal value (lmfit's transforms).  A two-sided parameter at
-// sin u = +-1 (on a bound) has slope exactly 0: it stays where it is.
-XM_DEV void bs_from_internal(int bt, double u, double lo, double hi, double& p, double& s) {
-  if (bt == XM_BS_TWO) {
-    double sn, cs;
-    sincos(u, &sn, &cs);
-    p = lo + (sn + 1.0) * (hi - lo) * 0.5;
-    s = (sn == 1.0 || sn == -1.0) ? 0.0 : cs * (hi - lo) * 0.5;
-  } else if (bt == XM_BS_LO) {
-    const double r = sqrt(u * u + 1.0);
-    p = lo - 1.0 + r;
-    s = u / r;
-  } else if (bt == XM_BS_HI) {
-    const double r = sqrt(u * u + 1.0);
-    p = hi + 1.0 - r;
-    s = -u / r;
-  } else {
-    p = u;
-    s = 1.0;
-  }
-}
-
-// internal value of the physical value v (clipped into its bounds): the inverse of bs_from_internal
-XM_DEV double bs_to_internal(int bt, double v, double lo, double hi) {
-  v = fmin(fmax(v, lo), hi);
-  if (bt == XM_BS_TWO) return asin(fmin(fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
-  if (bt == XM_BS_LO) return sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
-  if (bt == XM_BS_HI) return sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
-  return v;
+  const double s = wg_sum(red, c);
+  if (t == 0) bnorm[m] = sqrt(s);
 }
 
 // LDS layout of k_basis_fit (doubles): H[P*P] (upper: J^T J, lower: Cholesky factor), then vectors of P: hd (diag of
@@ -178,27 +140,13 @@ XM_DEV double bs_load_re(const BasisFitArgs& A, long long row, int i, double& im
   return x[0];
 }
 
-// every thread: the sum of red[0 ... NT) after a fixed tree
-XM_DEV double bs_reduce(const BsLds& L, double c) {
-  const int t = threadIdx.x;
-  L.red[t] = c;
-  __syncthreads();
-  for (int h = XM_BS_NT / 2; h > 0; h >>= 1) {
-    if (t < h) L.red[t] += L.red[t + h];
-    __syncthreads();
-  }
-  const double r = L.red[0];
-  __syncthreads();
-  return r;
-}
-
 // p, s <- physical values / slopes of the internal vector `u` (free parameters; fixed ones keep A.u0)
 XM_DEV void bs_set_params(const BasisFitArgs& A, const BsLds& L, const double* u) {
   const int t = threadIdx.x;
   if (t < A.Q) {
     const int j = A.col[t];
     double p = A.u0[t], s = 0.0;
-    if (j >= 0) bs_from_internal(A.bt[t], u[j], A.lo[t], A.hi[t], p, s);
+    if (j >= 0) wg_from_internal(A.bt[t], u[j], A.lo[t], A.hi[t], p, s);
     L.p[t] = p;
     L.s[t] = s;
   }
@@ -224,7 +172,7 @@ XM_DEV double bs_cost(const BasisFitArgs& A, const BsLds& L, long long row, doub
       fit[2 * (long long)i + 1] = mi;
     }
   }
-  return bs_reduce(L, c);
+  return wg_sum(L.red, c);
 }
 
 // [J | r] rows of point i into r0 (real part) and r1 (imaginary part).  `phys`: J with respect to the physical
@@ -345,53 +293,6 @@ XM_DEV void bs_normal(const BasisFitArgs& A, const BsLds& L, long long row, bool
   __syncthreads();
 }
 
-// Marquardt scale of a column: its largest squared norm so far, 1 for a column that has always been zero (MINPACK)
-XM_DEV double bs_scale(double d) { return d > 0.0 ? d : 1.0; }
-
-// Cholesky factor of H + lam diag(dsc) (upper triangle of H and hd; lam = 0: H itself) into the lower triangle of H and
-// ld.  Column by column, rows spread over the workgroup.  false (every thread alike) when not positive definite.
-XM_DEV bool bs_cholesky(const BasisFitArgs& A, const BsLds& L, double lam) {
-  const int t = threadIdx.x, P = A.P;
-  for (int j = 0; j < P; ++j) {
-    double s = L.hd[j] + lam * bs_scale(L.dsc[j]);
-    for (int k = 0; k < j; ++k) s -= L.H[j * P + k] * L.H[j * P + k];
-    if (!(s > 0.0) || !isfinite(s)) {
-      __syncthreads();
-      return false;
-    }
-    const double dj = sqrt(s);
-    for (int i = j + 1 + t; i < P; i += XM_BS_NT) {
-      double v = L.H[j * P + i];
-      for (int k = 0; k < j; ++k) v -= L.H[i * P + k] * L.H[j * P + k];
-      L.H[i * P + j] = v / dj;
-    }
-    if (t == 0) L.ld[j] = dj;
-    __syncthreads();
-  }
-  return true;
-}
-
-// dl <- (L L^T)^{-1} g; true when every component is finite
-XM_DEV bool bs_solve(const BasisFitArgs& A, const BsLds& L) {
-  const int P = A.P;
-  if (threadIdx.x == 0) {
-    for (int j = 0; j < P; ++j) {
-      double v = L.g[j];
-      for (int k = 0; k < j; ++k) v -= L.H[j * P + k] * L.dl[k];
-      L.dl[j] = v / L.ld[j];
-    }
-    for (int j = P - 1; j >= 0; --j) {
-      double v = L.dl[j];
-      for (int k = j + 1; k < P; ++k) v -= L.H[k * P + j] * L.dl[k];
-      L.dl[j] = v / L.ld[j];
-    }
-  }
-  __syncthreads();
-  bool ok = true;
-  for (int j = 0; j < P; ++j) ok = ok && isfinite(L.dl[j]);
-  return ok;
-}
-
 // one voxel: start, Levenberg-Marquardt, CRLB pass, outputs
 XM_DEV void bs_fit_row(const BasisFitArgs& A, const BsLds& L, long long row) {
   const int t = threadIdx.x, P = A.P, M = A.M, Q = A.Q;
@@ -403,12 +304,12 @@ XM_DEV void bs_fit_row(const BasisFitArgs& A, const BsLds& L, long long row) {
     const double xr = bs_load_re(A, row, i, xi);
     xx += xr * xr + xi * xi;
   }
-  const double xnorm = sqrt(bs_reduce(L, xx));
+  const double xnorm = sqrt(wg_sum(L.red, xx));
   if (t < Q && A.col[t] >= 0) {
     double u = A.u0[t];
     if (t < M && isnan(u)) {
       const double bn = A.bnorm[t];
-      u = bs_to_internal(A.bt[t], bn > 0.0 ? xnorm / ((double)M * bn) : 0.0, A.lo[t], A.hi[t]);
+      u = wg_to_internal(A.bt[t], bn > 0.0 ? xnorm / ((double)M * bn) : 0.0, A.lo[t], A.hi[t]);
     }
     L.u[A.col[t]] = u;
   }
@@ -429,8 +330,8 @@ XM_DEV void bs_fit_row(const BasisFitArgs& A, const BsLds& L, long long row) {
       need_jac = false;
     }
     ++it;
-    bool ok = bs_cholesky(A, L, lam);
-    if (ok) ok = bs_solve(A, L);
+    bool ok = wg_cholesky(L.H, L.hd, L.dsc, L.ld, P, lam);
+    if (ok) ok = wg_solve(L.H, L.ld, L.g, L.dl, P);
     if (!ok) {
       lam *= nu;
       nu *= 2.0;
@@ -439,7 +340,7 @@ XM_DEV void bs_fit_row(const BasisFitArgs& A, const BsLds& L, long long row) {
     }
     double dn = 0.0, un = 0.0, pred = 0.0;
     for (int j = 0; j < P; ++j) {
-      const double dj = bs_scale(L.dsc[j]);
+      const double dj = wg_lm_scale(L.dsc[j]);
       const double sd = sqrt(dj) * L.dl[j], su = sqrt(dj) * L.u[j];
       dn += sd * sd;
       un += su * su;
@@ -477,7 +378,7 @@ XM_DEV void bs_fit_row(const BasisFitArgs& A, const BsLds& L, long long row) {
   if (status != 2) {
     // CRLB: (J^T J)^{-1} with J over the physical free columns at the solution; the caller scales by sigma
     bs_normal(A, L, row, true);
-    const bool ok = bs_cholesky(A, L, 0.0);
+    const bool ok = wg_cholesky(L.H, L.hd, L.dsc, L.ld, P, 0.0);
     const int cap = stage_doubles / P;  // amplitudes per pass: each thread's forward substitution has P doubles
     for (int base = 0; base < M; base += cap) {
       const int m = base + t;
@@ -537,10 +438,7 @@ __global__ __launch_bounds__(XM_BS_NT) void k_basis_fit(BasisFitArgs A) {
   __shared__ unsigned next;
 
   for (;;) {
-    if (t == 0) next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long row = (long long)next;
-    __syncthreads();
+    const long long row = wg_next_item(A.counter, &next);
     if (row >= A.nb) break;
 
     // The voxel's arguments are read again from the kernel-argument segment: carried across this loop in scalar
@@ -549,12 +447,5 @@ __global__ __launch_bounds__(XM_BS_NT) void k_basis_fit(BasisFitArgs A) {
     asm volatile("" : "+s"(z));
     bs_fit_row((&A)[z], L, row);
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

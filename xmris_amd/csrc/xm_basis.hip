@@ -112,7 +112,7 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
     A.hi[q] = hi;
     if (is_fixed) {
       if (automatic) return bs_fail(who + "a fixed amplitude needs a value");
-      A.bt[q] = XM_BS_FIXED;
+      A.bt[q] = XM_WG_FIXED;
       A.col[q] = -1;
       A.u0[q] = std::fmin(std::fmax(init[q], lo), hi);
       continue;
@@ -120,17 +120,17 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
     if (P >= XM_BS_MAXP) return bs_fail("more than " + std::to_string(XM_BS_MAXP) + " free parameters");
     A.col[q] = (signed char)P++;
     const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
-    A.bt[q] = fl && fh ? XM_BS_TWO : fl ? XM_BS_LO : fh ? XM_BS_HI : XM_BS_FREE;
+    A.bt[q] = fl && fh ? XM_WG_TWO : fl ? XM_WG_LO : fh ? XM_WG_HI : XM_WG_FREE;
     if (automatic) {
       A.u0[q] = NAN;  // the kernel starts it per voxel
       continue;
     }
     const double v = std::fmin(std::fmax(init[q], lo), hi);  // initial values are clipped into their bounds
-    if (A.bt[q] == XM_BS_TWO)
+    if (A.bt[q] == XM_WG_TWO)
       A.u0[q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
-    else if (A.bt[q] == XM_BS_LO)
+    else if (A.bt[q] == XM_WG_LO)
       A.u0[q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
-    else if (A.bt[q] == XM_BS_HI)
+    else if (A.bt[q] == XM_WG_HI)
       A.u0[q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
     else
       A.u0[q] = v;
@@ -168,18 +168,11 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
 
   DeviceGuard guard(in);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   hipLaunchKernelGGL(k_basis_norms, dim3((unsigned)M), dim3(XM_BS_NT), 0, st, A.basis, n, skip,
                      (double*)((char*)workspace + 256));
   HIP_TRY(hipGetLastError());
-  const size_t lds = bs_lds_bytes(P, A.lda, A.q_pts);
-  int resident = 0;
-  if (const int rc = xm_resident_blocks(g_bs_res, k_basis_fit, XM_BS_NT, lds, &resident, st)) return rc;
-  const long long blocks = n_batch < resident ? n_batch : resident;
-  xm_note_kernel("k_basis_fit", nullptr, "fma", P, M);  // <J^T J form, free columns, metabolites>
-  hipLaunchKernelGGL(k_basis_fit, dim3((unsigned)blocks), dim3(XM_BS_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(g_bs_res, k_basis_fit, XM_BS_NT, bs_lds_bytes(P, A.lda, A.q_pts), n_batch, A, st, "k_basis_fit",
+                         "fma", P, M);  // <J^T J form, free columns, metabolites>
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // Coil combination kernel (the project's own definition, the reference has no such function).
-// Included by xm_coils.hip, and by xm_denoise.h for the staging, Gram, mirror, sum and Jacobi functions.
+// Included by xm_coils.hip, and by xm_denoise.h for the staging and Gram functions.  The block sum, the mirror, the
+// Gram maps and stores, the Jacobi iteration and the voxel ticket are xm_wg.h's.
 //
 // One voxel: X = its C x N FIDs (coil by time), R = the same voxel of the reference (or X), Linv = L^{-1} of the noise
 // covariance Psi = L L^H (or the identity).  G = Linv (R R^H) Linv^H; u = the eigenvector of G's largest eigenvalue
@@ -19,18 +20,16 @@
 // The order over time never depends on the batch or on the workgroup.  With fewer than 4 blocks (C <= 16) the four
 // waves take a quarter of each tile's points each and the four partial matrices are added in wave order.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_CC_MAXC 64
 #define XM_CC_NT 256
 #define XM_CC_Q 64       // time points per staged tile
 #define XM_CC_LDQ 68     // row stride of the staged tile in doubles: lanes (i, k) of an MFMA operand hit banks 4 i + k
-#define XM_CC_MAXE 9     // upper-triangle entries of G per thread, FMA form: ceil(64 * 65 / 2 / 256)
-#define XM_CC_MAXB 9     // 16 x 16 blocks per wave, MFMA form: ceil(36 / 4)
-#define XM_CC_SWEEPS 30  // Jacobi sweep cap (status 3)
 #define XM_CC_SMALL 1824 // doubles after the two matrices: scr[1024], red[256], w[128], u[128], rot[256], pairs[32]
-
-typedef double cc_d4 __attribute__((ext_vector_type(4)));
+static_assert(XM_CC_NT == XM_WG_NT, "k_coil_combine runs xm_wg.h's workgroup");
+static_assert(XM_CC_MAXC * (XM_CC_MAXC + 1) / 2 <= XM_WG_MAXE * XM_WG_NT, "the FMA form's slots must hold XM_CC_MAXC coils");
+static_assert((XM_CC_MAXC / 8) * (XM_CC_MAXC / 8 + 1) / 2 <= 4 * XM_WG_MAXB, "the MFMA form's slots must hold XM_CC_MAXC coils");
 
 struct CoilArgs {
   const void* x;       // (n_outer, C, n_inner, N) complex64 / complex128
@@ -45,10 +44,9 @@ struct CoilArgs {
   unsigned* counter;   // [2] zero at launch: voxel ticket, workgroups done
 };
 
-__host__ __device__ inline int cc_pad8(int C) { return (C + 7) & ~7; }
 // doubles of the second LDS matrix: the staged tile, then L^{-1} G, then the eigenvectors
 __host__ __device__ inline size_t cc_b_doubles(int C) {
-  const size_t stage = 2 * (size_t)cc_pad8(C) * XM_CC_LDQ, mat = 2 * (size_t)C * C;
+  const size_t stage = 2 * (size_t)wg_pad8(C) * XM_CC_LDQ, mat = 2 * (size_t)C * C;
   return stage > mat ? stage : mat;
 }
 __host__ __device__ inline size_t cc_lds_bytes(int C) {
@@ -76,26 +74,12 @@ XM_DEV void cc_load(const void* p, int c128, long long i, double& re, double& im
   }
 }
 
-// sum of v over the workgroup, the same value in every thread (fixed tree)
-XM_DEV double cc_sum(const CcLds& L, double v) {
-  const int t = threadIdx.x;
-  L.red[t] = v;
-  __syncthreads();
-  for (int h = XM_CC_NT / 2; h > 0; h >>= 1) {
-    if (t < h) L.red[t] += L.red[t + h];
-    __syncthreads();
-  }
-  const double r = L.red[0];
-  __syncthreads();
-  return r;
-}
-
 // tile [t0, t0 + Q) of R into Y (the B matrix); flags: bit 0 a non-finite sample, bit 1 a nonzero one.  GATHER
 // (k_denoise, xm_denoise.h): row c starts at rows[c], a table in the LDS, instead of V.roff + c V.rcs
 template <bool GATHER = false>
 XM_DEV void cc_stage(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int t0, int& flags,
                      const long long* rows = nullptr) {
-  const int t = threadIdx.x, tt = t & (XM_CC_Q - 1), Cp = cc_pad8(A.C);
+  const int t = threadIdx.x, tt = t & (XM_CC_Q - 1), Cp = wg_pad8(A.C);
   for (int c = t / XM_CC_Q; c < Cp; c += XM_CC_NT / XM_CC_Q) {
     double re = 0.0, im = 0.0;
     if (c < A.C && t0 + tt < A.NR) {
@@ -108,49 +92,19 @@ XM_DEV void cc_stage(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int t0
   }
 }
 
-// lower triangle <- conjugate of the upper one, diagonal real
-XM_DEV void cc_mirror(const CcLds& L, int C) {
-  for (int e = threadIdx.x; e < C * C; e += XM_CC_NT) {
-    const int i = e / C, j = e - i * C;
-    if (i > j) {
-      L.G[2 * e] = L.G[2 * (j * C + i)];
-      L.G[2 * e + 1] = -L.G[2 * (j * C + i) + 1];
-    } else if (i == j) {
-      L.G[2 * e + 1] = 0.0;
-    }
-  }
-  __syncthreads();
-}
-
 // G <- R R^H by plain FMAs: thread t owns entries t + 256 m of the upper triangle in row-major order
 template <bool GATHER = false>
 XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags,
                         const long long* rows = nullptr) {
   const int t = threadIdx.x, C = A.C, ne = C * (C + 1) / 2;
-  int ci[XM_CC_MAXE], cj[XM_CC_MAXE];
-  double re[XM_CC_MAXE], im[XM_CC_MAXE];
-  {
-    int i = 0, j = 0, e = 0;
-#pragma unroll
-    for (int m = 0; m < XM_CC_MAXE; ++m) {
-      const int target = t + XM_CC_NT * m;
-      while (e < target && e < ne) {
-        ++e;
-        if (++j >= C) {
-          ++i;
-          j = i;
-        }
-      }
-      ci[m] = i < C ? i : 0;
-      cj[m] = i < C ? j : 0;
-      re[m] = im[m] = 0.0;
-    }
-  }
+  int ci[XM_WG_MAXE], cj[XM_WG_MAXE];
+  double re[XM_WG_MAXE] = {}, im[XM_WG_MAXE] = {};
+  wg_gram_entries(C, ne, ci, cj);
   for (int t0 = 0; t0 < A.NR; t0 += XM_CC_Q) {
     cc_stage<GATHER>(A, L, V, t0, flags, rows);
     __syncthreads();
 #pragma unroll
-    for (int m = 0; m < XM_CC_MAXE; ++m) {
+    for (int m = 0; m < XM_WG_MAXE; ++m) {
       if (t + XM_CC_NT * m < ne) {
         const double* ai = L.B + (size_t)(2 * ci[m]) * XM_CC_LDQ;
         const double* aj = L.B + (size_t)(2 * cj[m]) * XM_CC_LDQ;
@@ -163,48 +117,28 @@ XM_DEV void cc_gram_fma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int m = 0; m < XM_CC_MAXE; ++m) {
-    if (t + XM_CC_NT * m < ne) {
-      L.G[2 * (ci[m] * C + cj[m])] = re[m];
-      L.G[2 * (ci[m] * C + cj[m]) + 1] = im[m];
-    }
-  }
-  __syncthreads();
-  cc_mirror(L, C);
+  wg_gram_entries_finish(L.G, C, ne, ci, cj, re, im);
 }
 
-// G <- R R^H on the fp64 matrix cores.  Work items j = slice * nblk + blk (blk: a 16 x 16 block (I, J), I <= J, of
-// Y Y^T; slice: a quarter of each tile's points when nblk < 4, else the whole tile); wave v takes items v, v + 4, ...
-// Operands of v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], i.e. Y[16 I + (l & 15)][k]
-// and Y[16 J + (l & 15)][k] with k = 4 kk + (l >> 4); result r of lane l is row (l >> 4) + 4 r, column l & 15.
+// G <- R R^H on the fp64 matrix cores, work items (block (I, J), slice) as wg_gram_items hands them out.  Operands of
+// v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15], i.e. Y[16 I + (l & 15)][k] and
+// Y[16 J + (l & 15)][k] with k = 4 kk + (l >> 4).
 template <bool GATHER = false>
 XM_DEV void cc_gram_mfma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, int& flags,
                          const long long* rows = nullptr) {
   const int t = threadIdx.x, C = A.C, wave = t >> 6, lane = t & 63;
-  const int nb = cc_pad8(C) / 8, nblk = nb * (nb + 1) / 2, S = nblk < 4 ? 4 : 1, nitems = nblk * S;
+  const int nb = wg_pad8(C) / 8, nblk = nb * (nb + 1) / 2, S = nblk < 4 ? 4 : 1, nitems = nblk * S;
   const int ksteps = XM_CC_Q / 4 / S;
-  int bi[XM_CC_MAXB], bj[XM_CC_MAXB], sl[XM_CC_MAXB];
-  cc_d4 acc[XM_CC_MAXB];
+  int bi[XM_WG_MAXB], bj[XM_WG_MAXB], sl[XM_WG_MAXB];
+  wg_d4 acc[XM_WG_MAXB];
+  wg_gram_items(nb, nblk, bi, bj, sl);
 #pragma unroll
-  for (int m = 0; m < XM_CC_MAXB; ++m) {
-    const int item = wave + 4 * m, blk = item % nblk;
-    int i = 0, j = 0;
-    for (int e = 0; e < blk; ++e)
-      if (++j >= nb) {
-        ++i;
-        j = i;
-      }
-    bi[m] = i;
-    bj[m] = j;
-    sl[m] = item / nblk;
-    acc[m] = cc_d4{0.0, 0.0, 0.0, 0.0};
-  }
+  for (int m = 0; m < XM_WG_MAXB; ++m) acc[m] = wg_d4{0.0, 0.0, 0.0, 0.0};
   for (int t0 = 0; t0 < A.NR; t0 += XM_CC_Q) {
     cc_stage<GATHER>(A, L, V, t0, flags, rows);
     __syncthreads();
 #pragma unroll
-    for (int m = 0; m < XM_CC_MAXB; ++m) {
+    for (int m = 0; m < XM_WG_MAXB; ++m) {
       if (wave + 4 * m < nitems) {  // wave-uniform: the MFMA runs with every lane on
         const int k0 = 4 * ksteps * sl[m] + (lane >> 4);
         const double* ya = L.B + (size_t)(16 * bi[m] + (lane & 15)) * XM_CC_LDQ + k0;
@@ -215,36 +149,9 @@ XM_DEV void cc_gram_mfma(const CoilArgs& A, const CcLds& L, const CcVoxel& V, in
     }
     __syncthreads();
   }
-  // every block through its wave's scratch square into G (or into its slice's partial matrix, in B: the tile is done)
-  double* scr = L.scr + 256 * wave;
-#pragma unroll
-  for (int m = 0; m < XM_CC_MAXB; ++m) {
-    const bool on = wave + 4 * m < nitems;
-    if (on)
-      for (int r = 0; r < 4; ++r) scr[((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc[m][r];
-    __syncthreads();
-    if (on) {
-      const int ii = lane >> 3, jj = lane & 7, i = 8 * bi[m] + ii, j = 8 * bj[m] + jj;
-      if (i < C && j < C && i <= j) {
-        double* dst = S == 1 ? L.G : L.B + (size_t)sl[m] * 2 * C * C;
-        dst[2 * (i * C + j)] = scr[(2 * ii) * 16 + 2 * jj] + scr[(2 * ii + 1) * 16 + 2 * jj + 1];
-        dst[2 * (i * C + j) + 1] = scr[(2 * ii + 1) * 16 + 2 * jj] - scr[(2 * ii) * 16 + 2 * jj + 1];
-      }
-    }
-    __syncthreads();
-  }
-  if (S > 1) {
-    const size_t m2 = 2 * (size_t)C * C;
-    for (int e = t; e < C * C; e += XM_CC_NT) {
-      const int i = e / C, j = e - i * C;
-      if (i <= j) {
-        L.G[2 * e] = ((L.B[2 * e] + L.B[m2 + 2 * e]) + L.B[2 * m2 + 2 * e]) + L.B[3 * m2 + 2 * e];
-        L.G[2 * e + 1] = ((L.B[2 * e + 1] + L.B[m2 + 2 * e + 1]) + L.B[2 * m2 + 2 * e + 1]) + L.B[3 * m2 + 2 * e + 1];
-      }
-    }
-    __syncthreads();
-  }
-  cc_mirror(L, C);
+  // the slices' partial matrices go to B: the tile is done
+  wg_gram_store(acc, bi, bj, sl, nitems, S, L.scr, L.G, L.B, C);
+  wg_gram_finish(L.G, L.B, C, S);
 }
 
 // G <- Linv G Linv^H through B
@@ -277,128 +184,7 @@ XM_DEV void cc_whiten(const CoilArgs& A, const CcLds& L) {
     L.G[2 * e + 1] = si;
   }
   __syncthreads();
-  cc_mirror(L, C);
-}
-
-// Parallel cyclic Jacobi on the Hermitian G (LDS), eigenvectors accumulated in B.  Round-robin pairing of
-// 2 ceil(C / 2) players (an odd C has a bye); the rotations of a step are computed by one thread each and applied by
-// the workgroup: columns of G and V, then rows of G.  A pair (p, q) with G_pq = h e^{i phi}:
-// J = [[c, s e^{i phi}], [-s e^{-i phi}, c]], tau = (G_qq - G_pp) / (2 h), t = sign(tau) / (|tau| + sqrt(1 + tau^2)).
-// Every update is written as x - s (y + r x), y + s (x - r y) with r = s / (1 + c) (Rutishauser), and the pair's
-// diagonal as G_pp - t h, G_qq + t h, so that a small rotation leaves a small rounding error.  Returns the sweeps done,
-// XM_CC_SWEEPS + 1 when the off-diagonal norm never fell to eps ||G||_F, -1 when ||G||_F^2 is not finite.  Both
-// norms are taken on G times the power of two that brings its largest diagonal entry to [1, 2), so the squares of small
-// samples do not underflow to a test that is met at once (a G that is itself subnormal or zero is not helped by it).
-#define XM_CC_ROT 8  // doubles per rotation: c, s, cos phi, sin phi, r, new G_pp, new G_qq
-XM_DEV int cc_jacobi(const CcLds& L, int C) {
-  const int t = threadIdx.x, np = (C + 1) / 2, players = 2 * np;
-  double* Vm = L.B;
-  for (int e = t; e < C * C; e += XM_CC_NT) {
-    Vm[2 * e] = (e / C == e % C) ? 1.0 : 0.0;
-    Vm[2 * e + 1] = 0.0;
-  }
-  double gmax = 0.0;  // (every thread alike: G is complete since cc_mirror's barrier)
-  for (int i = 0; i < C; ++i) gmax = fmax(gmax, fabs(L.G[2 * (i * C + i)]));
-  const int ex = gmax > 0.0 && isfinite(gmax) ? -ilogb(gmax) : 0;  // both norms on 2^ex G: exact, and no square underflows
-  double f = 0.0;
-  for (int e = t; e < 2 * C * C; e += XM_CC_NT) {
-    const double g = ldexp(L.G[e], ex);
-    f += g * g;
-  }
-  const double fro2 = cc_sum(L, f);  // (also the barrier after V's initialisation)
-  // samples so large that G or its norm overflows: nothing to iterate on
-  if (!isfinite(fro2) || !isfinite(ldexp(fro2, -2 * ex))) return -1;
-  const double eps = 2.220446049250313e-16;
-  int* pq = (int*)(L.rot + XM_CC_ROT * 32);  // pairs of the step, after the 32 rotations
-  for (int sweep = 0;; ++sweep) {
-    double o = 0.0;
-    for (int e = t; e < C * C; e += XM_CC_NT)
-      if (e / C != e % C) {
-        const double gr = ldexp(L.G[2 * e], ex), gi = ldexp(L.G[2 * e + 1], ex);
-        o += gr * gr + gi * gi;
-      }
-    const double off2 = cc_sum(L, o);
-    if (!(off2 > eps * eps * fro2)) return sweep;
-    if (sweep == XM_CC_SWEEPS) return XM_CC_SWEEPS + 1;
-    for (int step = 0; step < players - 1; ++step) {
-      if (t < np) {
-        int a = t == 0 ? players - 1 : (step + t) % (players - 1);
-        int b = t == 0 ? step : (step - t + players - 1) % (players - 1);
-        const int p = a < b ? a : b, q = a < b ? b : a;
-        double* r = L.rot + XM_CC_ROT * t;
-        r[0] = 1.0;
-        r[1] = 0.0;
-        if (q < C) {
-          const double gr = L.G[2 * (p * C + q)], gi = L.G[2 * (p * C + q) + 1];
-          const double h = hypot(gr, gi);
-          if (h > 0.0) {
-            const double gpp = L.G[2 * (p * C + p)], gqq = L.G[2 * (q * C + q)];
-            const double tau = (gqq - gpp) / (2.0 * h);
-            const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
-            r[0] = c;
-            r[1] = s;
-            r[2] = gr / h;
-            r[3] = gi / h;
-            r[4] = s / (1.0 + c);
-            r[5] = gpp - tt * h;
-            r[6] = gqq + tt * h;
-          }
-        }
-        pq[2 * t] = p;
-        pq[2 * t + 1] = q;
-      }
-      __syncthreads();
-      // columns: M[:, p] <- c M[:, p] - s e^{-i phi} M[:, q],  M[:, q] <- s e^{i phi} M[:, p] + c M[:, q]; M = G, V
-      for (int it = t; it < 2 * C * np; it += XM_CC_NT) {
-        const int e = it % (C * np), k = e % np, row = e / np;
-        const double* r = L.rot + XM_CC_ROT * k;
-        const double s = r[1];
-        if (s == 0.0) continue;  // nothing to rotate (or the bye)
-        const double er = r[2], ei = r[3], rr = r[4];
-        double* M = it < C * np ? L.G : Vm;
-        double* xp = M + 2 * (row * C + pq[2 * k]);
-        double* xq = M + 2 * (row * C + pq[2 * k + 1]);
-        const double xr = xp[0], xi = xp[1], yr = xq[0], yi = xq[1];
-        const double ar = yr * er + yi * ei, ai = yi * er - yr * ei;  // e^{-i phi} y
-        const double br = xr * er - xi * ei, bi = xi * er + xr * ei;  // e^{i phi} x
-        xp[0] = xr - s * (ar + rr * xr);
-        xp[1] = xi - s * (ai + rr * xi);
-        xq[0] = yr + s * (br - rr * yr);
-        xq[1] = yi + s * (bi - rr * yi);
-      }
-      __syncthreads();
-      // rows: G[p, :] <- c G[p, :] - s e^{i phi} G[q, :],  G[q, :] <- s e^{-i phi} G[p, :] + c G[q, :]; the pair's own
-      // 2 x 2 block is diagonal and real by construction and is stored so
-      for (int it = t; it < C * np; it += XM_CC_NT) {
-        const int k = it % np, j = it / np;
-        const double* r = L.rot + XM_CC_ROT * k;
-        const double s = r[1];
-        if (s == 0.0) continue;
-        const double er = r[2], ei = r[3], rr = r[4];
-        const int p = pq[2 * k], q = pq[2 * k + 1];
-        double* xp = L.G + 2 * (p * C + j);
-        double* xq = L.G + 2 * (q * C + j);
-        const double xr = xp[0], xi = xp[1], yr = xq[0], yi = xq[1];
-        const double ar = yr * er - yi * ei, ai = yi * er + yr * ei;  // e^{i phi} y
-        const double br = xr * er + xi * ei, bi = xi * er - xr * ei;  // e^{-i phi} x
-        double pr = xr - s * (ar + rr * xr), pi = xi - s * (ai + rr * xi);
-        double qr = yr + s * (br - rr * yr), qi = yi + s * (bi - rr * yi);
-        if (j == p) {
-          pr = r[5];
-          pi = qr = qi = 0.0;
-        } else if (j == q) {
-          qr = r[6];
-          qi = pr = pi = 0.0;
-        }
-        xp[0] = pr;
-        xp[1] = pi;
-        xq[0] = qr;
-        xq[1] = qi;
-      }
-      __syncthreads();
-    }
-  }
+  wg_mirror(L.G, C);
 }
 
 // the outputs of a voxel that is not combined: y and w zero, quality 0 (status 1) or NaN (status 2)
@@ -552,8 +338,8 @@ XM_DEV int cc_first_point(const CoilArgs& A, const CcLds& L, const CcVoxel& V, d
       __syncthreads();
     }
   }
-  ugu = cc_sum(L, su);
-  tr = cc_sum(L, st);
+  ugu = wg_sum(L.red, su);
+  tr = wg_sum(L.red, st);
   return __syncthreads_or(flags & 1) | (__syncthreads_or(flags & 2) ? 2 : 0) | (flags & 4);
 }
 
@@ -575,10 +361,7 @@ __global__ __launch_bounds__(XM_CC_NT, 2) void k_coil_combine(CoilArgs A) {
   __shared__ unsigned next;
 
   for (;;) {
-    if (t == 0) next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long v = (long long)next;
-    __syncthreads();
+    const long long v = wg_next_item(A.counter, &next);
     if (v >= A.nv) break;
     const long long a = v / A.n_inner, b = v - a * A.n_inner;
     CcVoxel V;
@@ -607,8 +390,8 @@ __global__ __launch_bounds__(XM_CC_NT, 2) void k_coil_combine(CoilArgs A) {
     if (FORM != XM_CC_FORM_FIRST) {
       if (A.linv) cc_whiten(A, L);
       for (int c = 0; c < C; ++c) tr += L.G[2 * (c * C + c)];
-      const int sweeps = cc_jacobi(L, C);
-      if (sweeps > XM_CC_SWEEPS) status = 3;
+      const int sweeps = wg_jacobi(L.G, L.B, L.red, L.rot, C);
+      if (sweeps > XM_WG_SWEEPS) status = 3;
       int best = 0;  // the largest diagonal entry, the lowest index on a tie
       for (int c = 1; c < C; ++c)
         if (L.G[2 * (c * C + c)] > L.G[2 * (best * C + best)]) best = c;
@@ -658,12 +441,5 @@ __global__ __launch_bounds__(XM_CC_NT, 2) void k_coil_combine(CoilArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

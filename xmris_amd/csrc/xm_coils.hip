@@ -11,15 +11,8 @@ XmResidency g_cc_res[3];  // one residency record per kernel instantiation
 
 template <int FORM>
 int cc_launch(const CoilArgs& A, const char* form, hipStream_t st) {
-  const size_t lds = cc_lds_bytes(A.C);
-  int resident = 0;
-  const int rc = xm_resident_blocks(g_cc_res[FORM], k_coil_combine<FORM>, XM_CC_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = A.nv < resident ? A.nv : resident;
-  xm_note_kernel("k_coil_combine", nullptr, form, A.C, -1);  // <form, coils>
-  hipLaunchKernelGGL(k_coil_combine<FORM>, dim3((unsigned)blocks), dim3(XM_CC_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(g_cc_res[FORM], k_coil_combine<FORM>, XM_CC_NT, cc_lds_bytes(A.C), A.nv, A, st,
+                         "k_coil_combine", form, A.C, -1);  // <form, coils>
 }
 }  // namespace
 
@@ -58,7 +51,6 @@ extern "C" int xm_coil_combine(const void* x, const void* ref_or_null, void* y, 
 
   DeviceGuard guard(x);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   if (method == XM_COIL_FIRST_POINT) return cc_launch<XM_CC_FORM_FIRST>(A, "first_point", st);
   if (method == XM_COIL_SVD && C >= 8) return cc_launch<XM_CC_FORM_MFMA>(A, "mfma", st);
   return cc_launch<XM_CC_FORM_FMA>(A, "fma", st);  // below 8 coils a 16-row block would be mostly padding

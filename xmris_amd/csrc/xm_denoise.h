@@ -9,14 +9,16 @@
 //
 // k_denoise: one 256-thread workgroup per voxel, voxels handed out by a device counter (persistent grid, as
 // k_coil_combine).  The window's P row starts are formed once per voxel into the LDS; from there on a window is the
-// "coils" of k_coil_combine: the staging, the Gram matrix (matrix cores or plain FMAs), the mirror, the sum and the
-// Jacobi iteration are xm_coils.h's, on its LDS layout with C = P.  All arithmetic fp64; complex64 is widened on load.
+// "coils" of k_coil_combine: the staging and the Gram matrix (matrix cores or plain FMAs) are xm_coils.h's, on its LDS
+// layout with C = P; the Jacobi iteration (wg_jacobi) and the voxel ticket are xm_wg.h's.  All arithmetic fp64; complex64
+// is widened on load.
 #pragma once
 #include "xm_coils.h"
 
 #define XM_DN_MAXP 64
 #define XM_DN_MAXN 16384
 #define XM_DN_NT XM_CC_NT
+static_assert(XM_DN_NT == XM_WG_NT, "k_denoise runs xm_wg.h's workgroup");
 #define XM_DN_EXTRA 160  // doubles after xm_coils.h's layout: rows[64] (long long), lam[64], ord[64] (int)
 
 struct DenoiseArgs {
@@ -116,10 +118,7 @@ __global__ __launch_bounds__(XM_DN_NT, 2) void k_denoise(DenoiseArgs A) {
   const CcVoxel V{};  // (unused with a row table)
 
   for (;;) {
-    if (t == 0) next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long v = (long long)next;
-    __syncthreads();
+    const long long v = wg_next_item(A.counter, &next);
     if (v >= A.nv) break;
 
     // the window: start o_a = min(max(i_a - p_a / 2, 0), s_a - p_a) per patch dim, rows in row-major order
@@ -156,9 +155,9 @@ __global__ __launch_bounds__(XM_DN_NT, 2) void k_denoise(DenoiseArgs A) {
       __syncthreads();
       continue;
     }
-    const int sweeps = cc_jacobi(L, P);
-    if (sweeps < 0 || sweeps > XM_CC_SWEEPS) {
-      dn_degenerate(A, v, sweeps < 0 ? 2 : 3, NAN, sweeps > XM_CC_SWEEPS);
+    const int sweeps = wg_jacobi(L.G, L.B, L.red, L.rot, P);
+    if (sweeps < 0 || sweeps > XM_WG_SWEEPS) {
+      dn_degenerate(A, v, sweeps < 0 ? 2 : 3, NAN, sweeps > XM_WG_SWEEPS);
       __syncthreads();
       continue;
     }
@@ -232,12 +231,5 @@ __global__ __launch_bounds__(XM_DN_NT, 2) void k_denoise(DenoiseArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

@@ -11,15 +11,8 @@ XmResidency g_dn_res[2];  // one residency record per kernel instantiation
 
 template <int FORM>
 int dn_launch(const DenoiseArgs& A, hipStream_t st) {
-  const size_t lds = dn_lds_bytes(A.P);
-  int resident = 0;
-  const int rc = xm_resident_blocks(g_dn_res[FORM], k_denoise<FORM>, XM_DN_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = A.nv < resident ? A.nv : resident;
-  xm_note_kernel("k_denoise", nullptr, FORM == XM_DN_FORM_MFMA ? "mfma" : "fma", A.P, A.rank_in);  // <form, P[, rank]>
-  hipLaunchKernelGGL(k_denoise<FORM>, dim3((unsigned)blocks), dim3(XM_DN_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(g_dn_res[FORM], k_denoise<FORM>, XM_DN_NT, dn_lds_bytes(A.P), A.nv, A, st, "k_denoise",
+                         FORM == XM_DN_FORM_MFMA ? "mfma" : "fma", A.P, A.rank_in);  // <form, P[, rank]>
 }
 }  // namespace
 
@@ -66,7 +59,6 @@ extern "C" int xm_denoise_patches(const void* x, void* y, int32_t* rank_out, dou
 
   DeviceGuard guard(x);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   if ((dtype & XM_DENOISE_GRAM_FMA) || P < 8) return dn_launch<XM_DN_FORM_FMA>(A, st);  // below 8 rows a 16-row block would be mostly padding
   return dn_launch<XM_DN_FORM_MFMA>(A, st);
 }

@@ -181,3 +181,18 @@ inline bool xm_pair_loads_ok(const void* in, int64_t in_stride, int n_in, int pa
 // launchers note the kernel template, its plan and its mode words right before the launch -- reports quote this
 // instead of a string typed by hand.
 void xm_note_kernel(const char* base, const std::type_info* plan, const char* scalar, int mode, int opt);
+
+// One launch of a persistent per-item kernel (the row ticket of xm_wg.h): zeroes the counter pair A.counter, sizes the
+// grid to min(n_items, resident workgroups of the stream), notes the kernel as <name><form, mode, opt> and launches it.
+template <class K, class Args>
+int xm_launch_items(XmResidency& res, K kern, int nt, size_t lds, long long n_items, const Args& A, hipStream_t st,
+                    const char* name, const char* form, int mode, int opt) {
+  HIP_TRY(hipMemsetAsync(A.counter, 0, 2 * sizeof(unsigned), st));
+  int resident = 0;
+  if (const int rc = xm_resident_blocks(res, kern, nt, lds, &resident, st)) return rc;
+  const long long blocks = n_items < resident ? n_items : resident;
+  xm_note_kernel(name, nullptr, form, mode, opt);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(nt), lds, st, A);
+  HIP_TRY(hipGetLastError());
+  return XM_OK;
+}

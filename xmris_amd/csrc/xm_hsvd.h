@@ -14,10 +14,11 @@
 // parts 336 doubles on, which puts the two on opposite halves of the banks), and the real matrix Y of k_coil_combine,
 // rows 2 i = Re x[l + i] and 2 i + 1 = Im x[l + i], is never stored: lane (row r, step k) of an MFMA operand reads
 // part r & 1 of sample (r >> 1) + k.  Hankel rows past R are masked in the operand, not in the samples (a sample is
-// shared by up to M rows).  The upper block triangle of Y Y^T accumulates on v_mfma_f64_16x16x4_f64 exactly as in
-// cc_gram_mfma (same operand layout, same slicing in four when there are fewer than 4 blocks), or by plain FMAs, one
-// upper-triangle entry per thread slot (FORM = FMA).  Time order never depends on the batch or the workgroup.
-// Eigenvectors.  cc_jacobi's parallel cyclic Jacobi, then a stable selection of the K largest diagonal entries.
+// shared by up to M rows).  The upper block triangle of Y Y^T accumulates on v_mfma_f64_16x16x4_f64, work items, stores
+// and the slicing in four when there are fewer than 4 blocks being wg_gram_items / wg_gram_store / wg_gram_finish of
+// xm_wg.h, or by plain FMAs, one upper-triangle entry per thread slot (wg_gram_entries; FORM = FMA).  Time order never
+// depends on the batch or the workgroup.
+// Eigenvectors.  wg_jacobi's parallel cyclic Jacobi (xm_wg.h), then a stable selection of the K largest diagonal entries.
 // Poles.  Householder reduction of Q to Hessenberg form, then single-shift QR with Wilkinson's shift and deflation,
 // eigenvalues only (the active window alone is updated).  One QR step: lane j of wave 0 owns column j and applies the
 // Givens rotations of the step to it in order, rotation k being formed by lane k and passed on by v_readlane; then
@@ -26,7 +27,7 @@
 // every thread owns up to three entries of [B^H B | B^H x] and adds the tile's points in ascending order; complex
 // Cholesky in the LDS.  Subtract.  One thread per time point, the powers formed again the same way.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_HS_NT 256
 #define XM_HS_MAXM 64
@@ -34,18 +35,15 @@
 #define XM_HS_MAXN 16384
 #define XM_HS_Q 256       // Hankel rows per staged tile
 #define XM_HS_SEG 336     // doubles per part of the staged samples (Q + 64 used)
-#define XM_HS_MAXE 9      // upper-triangle entries of G per thread, FMA form: ceil(64 * 65 / 2 / 256)
-#define XM_HS_MAXB 9      // 16 x 16 blocks per wave, MFMA form: ceil(36 / 4)
-#define XM_HS_SWEEPS 30   // Jacobi sweep cap (status 3)
 #define XM_HS_T 128       // time points per tile of the amplitude stage
 #define XM_HS_LDT 129     // row stride of that tile in doubles
 #define XM_HS_MAXP 3      // entries of [B^H B | B^H x] per thread: ceil((32 * 33 / 2 + 32) / 256)
-#define XM_HS_ROT 8       // doubles per Jacobi rotation
 // doubles after the big region: seg[672], scr[1024], red[256], rot[256 + 32], lam[64], z[64], lz[64], a[64], f[32], d[32],
 // ints[64 as 32 doubles]
 #define XM_HS_SMALL 2648
-
-typedef double hs_d4 __attribute__((ext_vector_type(4)));
+static_assert(XM_HS_NT == XM_WG_NT, "k_hsvd runs xm_wg.h's workgroup");
+static_assert(XM_HS_MAXM * (XM_HS_MAXM + 1) / 2 <= XM_WG_MAXE * XM_WG_NT, "the FMA form's slots must hold XM_HS_MAXM columns");
+static_assert((XM_HS_MAXM / 8) * (XM_HS_MAXM / 8 + 1) / 2 <= 4 * XM_WG_MAXB, "the MFMA form's slots must hold XM_HS_MAXM columns");
 
 // `stop` (timing only): end every FID after the named stage
 enum { XM_HS_STOP_NONE = 0, XM_HS_STOP_GRAM = 1, XM_HS_STOP_EIG = 2, XM_HS_STOP_POLES = 3, XM_HS_STOP_AMPL = 4 };
@@ -63,7 +61,6 @@ struct HsvdArgs {
   unsigned* counter;   // [2] zero at launch: row ticket, workgroups done
 };
 
-__host__ __device__ inline int hs_pad8(int M) { return (M + 7) & ~7; }
 // the eigenvector matrix, which first holds the four partial Gram matrices of the sliced form (M <= 16)
 __host__ __device__ inline size_t hs_v_doubles(int M) {
   const size_t mm = 2 * (size_t)M * M;
@@ -131,20 +128,6 @@ XM_DEV void hs_store(void* p, int c128, long long i, double re, double im) {
     ((float2*)p)[i] = make_float2((float)re, (float)im);
 }
 
-// sum of v over the workgroup, the same value in every thread (fixed tree)
-XM_DEV double hs_sum(const HsLds& L, double v) {
-  const int t = threadIdx.x;
-  L.red[t] = v;
-  __syncthreads();
-  for (int h = XM_HS_NT / 2; h > 0; h >>= 1) {
-    if (t < h) L.red[t] += L.red[t + h];
-    __syncthreads();
-  }
-  const double r = L.red[0];
-  __syncthreads();
-  return r;
-}
-
 // the value of lane `lane` (wave-uniform) in every lane of the wave
 XM_DEV double hs_bcast(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -166,48 +149,18 @@ XM_DEV void hs_stage(const HsvdArgs& A, const HsLds& L, long long xoff, int t0, 
   }
 }
 
-// lower triangle <- conjugate of the upper one, diagonal real
-XM_DEV void hs_mirror(const HsLds& L, int M) {
-  for (int e = threadIdx.x; e < M * M; e += XM_HS_NT) {
-    const int i = e / M, j = e - i * M;
-    if (i > j) {
-      L.G[2 * e] = L.G[2 * (j * M + i)];
-      L.G[2 * e + 1] = -L.G[2 * (j * M + i) + 1];
-    } else if (i == j) {
-      L.G[2 * e + 1] = 0.0;
-    }
-  }
-  __syncthreads();
-}
-
 // G[i][j] <- sum_l x[l + i] conj(x[l + j]) by plain FMAs: thread t owns entries t + 256 m of the upper triangle
 XM_DEV void hs_gram_fma(const HsvdArgs& A, const HsLds& L, long long xoff, int& flags) {
   const int t = threadIdx.x, M = A.M, ne = M * (M + 1) / 2, R = A.N - M + 1;
-  int ci[XM_HS_MAXE], cj[XM_HS_MAXE];
-  double re[XM_HS_MAXE], im[XM_HS_MAXE];
-  {
-    int i = 0, j = 0, e = 0;
-#pragma unroll
-    for (int m = 0; m < XM_HS_MAXE; ++m) {
-      const int target = t + XM_HS_NT * m;
-      while (e < target && e < ne) {
-        ++e;
-        if (++j >= M) {
-          ++i;
-          j = i;
-        }
-      }
-      ci[m] = i < M ? i : 0;
-      cj[m] = i < M ? j : 0;
-      re[m] = im[m] = 0.0;
-    }
-  }
+  int ci[XM_WG_MAXE], cj[XM_WG_MAXE];
+  double re[XM_WG_MAXE] = {}, im[XM_WG_MAXE] = {};
+  wg_gram_entries(M, ne, ci, cj);
   for (int t0 = 0; t0 < R; t0 += XM_HS_Q) {
     hs_stage(A, L, xoff, t0, flags);
     __syncthreads();
     const int lim = R - t0 < XM_HS_Q ? R - t0 : XM_HS_Q;
 #pragma unroll
-    for (int m = 0; m < XM_HS_MAXE; ++m) {
+    for (int m = 0; m < XM_WG_MAXE; ++m) {
       if (t + XM_HS_NT * m < ne) {
         const double* ai = L.seg + ci[m];
         const double* aj = L.seg + cj[m];
@@ -220,46 +173,27 @@ XM_DEV void hs_gram_fma(const HsvdArgs& A, const HsLds& L, long long xoff, int& 
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int m = 0; m < XM_HS_MAXE; ++m) {
-    if (t + XM_HS_NT * m < ne) {
-      L.G[2 * (ci[m] * M + cj[m])] = re[m];
-      L.G[2 * (ci[m] * M + cj[m]) + 1] = im[m];
-    }
-  }
-  __syncthreads();
-  hs_mirror(L, M);
+  wg_gram_entries_finish(L.G, M, ne, ci, cj, re, im);
 }
 
-// The same on the fp64 matrix cores; work items, operand and result layout as cc_gram_mfma (xm_coils.h): lane l holds
-// Y[16 I + (l & 15)][k] and Y[16 J + (l & 15)][k], k = 4 kk + (l >> 4); result r of lane l is row (l >> 4) + 4 r, column
-// l & 15.  Y[r][k] = part r & 1 of sample t0 + (r >> 1) + k, zero for Hankel rows t0 + k >= R.
+// The same on the fp64 matrix cores, work items (block (I, J), slice) as wg_gram_items hands them out: lane l holds
+// Y[16 I + (l & 15)][k] and Y[16 J + (l & 15)][k], k = 4 kk + (l >> 4).  Y[r][k] = part r & 1 of sample
+// t0 + (r >> 1) + k, zero for Hankel rows t0 + k >= R.
 XM_DEV void hs_gram_mfma(const HsvdArgs& A, const HsLds& L, long long xoff, int& flags) {
   const int t = threadIdx.x, M = A.M, wave = t >> 6, lane = t & 63, R = A.N - M + 1;
-  const int nb = hs_pad8(M) / 8, nblk = nb * (nb + 1) / 2, S = nblk < 4 ? 4 : 1, nitems = nblk * S;
+  const int nb = wg_pad8(M) / 8, nblk = nb * (nb + 1) / 2, S = nblk < 4 ? 4 : 1, nitems = nblk * S;
   const int ksteps = XM_HS_Q / 4 / S;
-  int bi[XM_HS_MAXB], bj[XM_HS_MAXB], sl[XM_HS_MAXB];
-  hs_d4 acc[XM_HS_MAXB];
+  int bi[XM_WG_MAXB], bj[XM_WG_MAXB], sl[XM_WG_MAXB];
+  wg_d4 acc[XM_WG_MAXB];
+  wg_gram_items(nb, nblk, bi, bj, sl);
 #pragma unroll
-  for (int m = 0; m < XM_HS_MAXB; ++m) {
-    const int item = wave + 4 * m, blk = item % nblk;
-    int i = 0, j = 0;
-    for (int e = 0; e < blk; ++e)
-      if (++j >= nb) {
-        ++i;
-        j = i;
-      }
-    bi[m] = i;
-    bj[m] = j;
-    sl[m] = item / nblk;
-    acc[m] = hs_d4{0.0, 0.0, 0.0, 0.0};
-  }
+  for (int m = 0; m < XM_WG_MAXB; ++m) acc[m] = wg_d4{0.0, 0.0, 0.0, 0.0};
   for (int t0 = 0; t0 < R; t0 += XM_HS_Q) {
     hs_stage(A, L, xoff, t0, flags);
     __syncthreads();
     const int lim = R - t0;  // Hankel rows of this tile: k < lim
 #pragma unroll
-    for (int m = 0; m < XM_HS_MAXB; ++m) {
+    for (int m = 0; m < XM_WG_MAXB; ++m) {
       if (wave + 4 * m < nitems) {  // wave-uniform: the MFMA runs with every lane on
         const int kb = 4 * ksteps * sl[m], k0 = kb + (lane >> 4);
         const int ra = 16 * bi[m] + (lane & 15), rb = 16 * bj[m] + (lane & 15);
@@ -279,148 +213,9 @@ XM_DEV void hs_gram_mfma(const HsvdArgs& A, const HsLds& L, long long xoff, int&
     }
     __syncthreads();
   }
-  // every block through its wave's scratch square into G (or into its slice's partial matrix, in V)
-  double* scr = L.scr + 256 * wave;
-#pragma unroll
-  for (int m = 0; m < XM_HS_MAXB; ++m) {
-    const bool on = wave + 4 * m < nitems;
-    if (on)
-      for (int r = 0; r < 4; ++r) scr[((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc[m][r];
-    __syncthreads();
-    if (on) {
-      const int ii = lane >> 3, jj = lane & 7, i = 8 * bi[m] + ii, j = 8 * bj[m] + jj;
-      if (i < M && j < M && i <= j) {
-        double* dst = S == 1 ? L.G : L.V + (size_t)sl[m] * 2 * M * M;
-        dst[2 * (i * M + j)] = scr[(2 * ii) * 16 + 2 * jj] + scr[(2 * ii + 1) * 16 + 2 * jj + 1];
-        dst[2 * (i * M + j) + 1] = scr[(2 * ii + 1) * 16 + 2 * jj] - scr[(2 * ii) * 16 + 2 * jj + 1];
-      }
-    }
-    __syncthreads();
-  }
-  if (S > 1) {
-    const size_t m2 = 2 * (size_t)M * M;
-    for (int e = t; e < M * M; e += XM_HS_NT) {
-      const int i = e / M, j = e - i * M;
-      if (i <= j) {
-        L.G[2 * e] = ((L.V[2 * e] + L.V[m2 + 2 * e]) + L.V[2 * m2 + 2 * e]) + L.V[3 * m2 + 2 * e];
-        L.G[2 * e + 1] = ((L.V[2 * e + 1] + L.V[m2 + 2 * e + 1]) + L.V[2 * m2 + 2 * e + 1]) + L.V[3 * m2 + 2 * e + 1];
-      }
-    }
-    __syncthreads();
-  }
-  hs_mirror(L, M);
-}
-
-// cc_jacobi (xm_coils.h) on G, eigenvectors in V: the sweeps done, XM_HS_SWEEPS + 1 at the cap, -1 when ||G||_F^2 is
-// not finite.  The norms of the stopping test are taken on G times a power of two, so small samples' squares do not
-// underflow to a test that is met at once; samples so small that G itself is subnormal or zero are not helped by it.
-XM_DEV int hs_jacobi(const HsLds& L, int C) {
-  const int t = threadIdx.x, np = (C + 1) / 2, players = 2 * np;
-  double* Vm = L.V;
-  for (int e = t; e < C * C; e += XM_HS_NT) {
-    Vm[2 * e] = (e / C == e % C) ? 1.0 : 0.0;
-    Vm[2 * e + 1] = 0.0;
-  }
-  double gmax = 0.0;  // (every thread alike: G is complete since hs_mirror's barrier)
-  for (int i = 0; i < C; ++i) gmax = fmax(gmax, fabs(L.G[2 * (i * C + i)]));
-  const int ex = gmax > 0.0 && isfinite(gmax) ? -ilogb(gmax) : 0;  // both norms on 2^ex G: exact, and no square underflows
-  double f = 0.0;
-  for (int e = t; e < 2 * C * C; e += XM_HS_NT) {
-    const double g = ldexp(L.G[e], ex);
-    f += g * g;
-  }
-  const double fro2 = hs_sum(L, f);  // (also the barrier after V's initialisation)
-  if (!isfinite(fro2) || !isfinite(ldexp(fro2, -2 * ex))) return -1;  // G, or ||G||_F^2 itself, not finite
-  const double eps = 2.220446049250313e-16;
-  int* pq = (int*)(L.rot + XM_HS_ROT * 32);  // pairs of the step, after the 32 rotations
-  for (int sweep = 0;; ++sweep) {
-    double o = 0.0;
-    for (int e = t; e < C * C; e += XM_HS_NT)
-      if (e / C != e % C) {
-        const double gr = ldexp(L.G[2 * e], ex), gi = ldexp(L.G[2 * e + 1], ex);
-        o += gr * gr + gi * gi;
-      }
-    const double off2 = hs_sum(L, o);
-    if (!(off2 > eps * eps * fro2)) return sweep;
-    if (sweep == XM_HS_SWEEPS) return XM_HS_SWEEPS + 1;
-    for (int step = 0; step < players - 1; ++step) {
-      if (t < np) {
-        int a = t == 0 ? players - 1 : (step + t) % (players - 1);
-        int b = t == 0 ? step : (step - t + players - 1) % (players - 1);
-        const int p = a < b ? a : b, q = a < b ? b : a;
-        double* r = L.rot + XM_HS_ROT * t;
-        r[0] = 1.0;
-        r[1] = 0.0;
-        if (q < C) {
-          const double gr = L.G[2 * (p * C + q)], gi = L.G[2 * (p * C + q) + 1];
-          const double h = hypot(gr, gi);
-          if (h > 0.0) {
-            const double gpp = L.G[2 * (p * C + p)], gqq = L.G[2 * (q * C + q)];
-            const double tau = (gqq - gpp) / (2.0 * h);
-            const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
-            r[0] = c;
-            r[1] = s;
-            r[2] = gr / h;
-            r[3] = gi / h;
-            r[4] = s / (1.0 + c);
-            r[5] = gpp - tt * h;
-            r[6] = gqq + tt * h;
-          }
-        }
-        pq[2 * t] = p;
-        pq[2 * t + 1] = q;
-      }
-      __syncthreads();
-      // columns of G and V
-      for (int it = t; it < 2 * C * np; it += XM_HS_NT) {
-        const int e = it % (C * np), k = e % np, row = e / np;
-        const double* r = L.rot + XM_HS_ROT * k;
-        const double s = r[1];
-        if (s == 0.0) continue;  // nothing to rotate (or the bye)
-        const double er = r[2], ei = r[3], rr = r[4];
-        double* Mx = it < C * np ? L.G : Vm;
-        double* xp = Mx + 2 * (row * C + pq[2 * k]);
-        double* xq = Mx + 2 * (row * C + pq[2 * k + 1]);
-        const double xr = xp[0], xi = xp[1], yr = xq[0], yi = xq[1];
-        const double ar = yr * er + yi * ei, ai = yi * er - yr * ei;  // e^{-i phi} y
-        const double br = xr * er - xi * ei, bi = xi * er + xr * ei;  // e^{i phi} x
-        xp[0] = xr - s * (ar + rr * xr);
-        xp[1] = xi - s * (ai + rr * xi);
-        xq[0] = yr + s * (br - rr * yr);
-        xq[1] = yi + s * (bi - rr * yi);
-      }
-      __syncthreads();
-      // rows of G; the pair's own 2 x 2 block is diagonal and real by construction and is stored so
-      for (int it = t; it < C * np; it += XM_HS_NT) {
-        const int k = it % np, j = it / np;
-        const double* r = L.rot + XM_HS_ROT * k;
-        const double s = r[1];
-        if (s == 0.0) continue;
-        const double er = r[2], ei = r[3], rr = r[4];
-        const int p = pq[2 * k], q = pq[2 * k + 1];
-        double* xp = L.G + 2 * (p * C + j);
-        double* xq = L.G + 2 * (q * C + j);
-        const double xr = xp[0], xi = xp[1], yr = xq[0], yi = xq[1];
-        const double ar = yr * er - yi * ei, ai = yi * er + yr * ei;  // e^{i phi} y
-        const double br = xr * er + xi * ei, bi = xi * er - xr * ei;  // e^{-i phi} x
-        double pr = xr - s * (ar + rr * xr), pi = xi - s * (ai + rr * xi);
-        double qr = yr + s * (br - rr * yr), qi = yi + s * (bi - rr * yi);
-        if (j == p) {
-          pr = r[5];
-          pi = qr = qi = 0.0;
-        } else if (j == q) {
-          qr = r[6];
-          qi = pr = pi = 0.0;
-        }
-        xp[0] = pr;
-        xp[1] = pi;
-        xq[0] = qr;
-        xq[1] = qi;
-      }
-      __syncthreads();
-    }
-  }
+  // the slices' partial matrices go to V
+  wg_gram_store(acc, bi, bj, sl, nitems, S, L.scr, L.G, L.V, M);
+  wg_gram_finish(L.G, L.V, M, S);
 }
 
 // W (M x K, into G's place) <- the eigenvectors of the K largest diagonal entries of G, the largest first, a tie going
@@ -714,7 +509,7 @@ XM_DEV int hs_amplitudes(const HsvdArgs& A, const HsLds& L, double* big, long lo
     }
   }
   __syncthreads();
-  // Cholesky, column by column, rows spread over the workgroup (am_cholesky of xm_amares.h, complex)
+  // Cholesky, column by column, rows spread over the workgroup (wg_cholesky of xm_wg.h, complex)
   for (int j = 0; j < K; ++j) {
     double s = Nm[2 * (j * K + j)];
     for (int k = 0; k < j; ++k) s -= hz_abs2(hz_ld(Nm, j * K + k));
@@ -787,7 +582,7 @@ __global__ __launch_bounds__(XM_HS_NT) void k_hsvd(HsvdArgs A) {
   L.scr = L.seg + 2 * XM_HS_SEG;
   L.red = L.scr + 1024;
   L.rot = L.red + XM_HS_NT;
-  L.lam = L.rot + XM_HS_ROT * 32 + 32;
+  L.lam = L.rot + XM_WG_ROT * 32 + 32;
   L.z = L.lam + XM_HS_MAXM;
   L.lz = L.z + 2 * XM_HS_MAXK;
   L.a = L.lz + 2 * XM_HS_MAXK;
@@ -797,10 +592,7 @@ __global__ __launch_bounds__(XM_HS_NT) void k_hsvd(HsvdArgs A) {
   __shared__ unsigned next;
 
   for (;;) {
-    if (t == 0) next = atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long v = (long long)next;
-    __syncthreads();
+    const long long v = wg_next_item(A.counter, &next);
     if (v >= A.nb) break;
     const long long xoff = v * A.stride;
 
@@ -817,10 +609,10 @@ __global__ __launch_bounds__(XM_HS_NT) void k_hsvd(HsvdArgs A) {
     }
     int status = 0;
     if (A.stop != XM_HS_STOP_GRAM) {
-      const int sweeps = hs_jacobi(L, M);
+      const int sweeps = wg_jacobi(L.G, L.V, L.red, L.rot, M);
       if (sweeps < 0)
         status = 2;  // finite samples so large that G or its squared norm overflows
-      else if (sweeps > XM_HS_SWEEPS)
+      else if (sweeps > XM_WG_SWEEPS)
         status = 3;
     }
     if (status == 0 && A.stop != XM_HS_STOP_GRAM && A.stop != XM_HS_STOP_EIG) {
@@ -830,7 +622,7 @@ __global__ __launch_bounds__(XM_HS_NT) void k_hsvd(HsvdArgs A) {
       } else {
         double f = 0.0;
         for (int e = t; e < 2 * K * K; e += XM_HS_NT) f += L.V[e] * L.V[e];
-        const double hnorm = sqrt(hs_sum(L, f));
+        const double hnorm = sqrt(wg_sum(L.red, f));
         hs_hessenberg(L, K);
         if (!hs_qr(L, K, hnorm))
           status = 3;
@@ -877,12 +669,5 @@ __global__ __launch_bounds__(XM_HS_NT) void k_hsvd(HsvdArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

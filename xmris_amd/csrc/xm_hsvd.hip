@@ -11,15 +11,8 @@ XmResidency g_hs_res[2];  // one residency record per kernel instantiation
 
 template <int FORM>
 int hs_launch(const HsvdArgs& A, hipStream_t st) {
-  const size_t lds = hs_lds_bytes(A.M, A.K);
-  int resident = 0;
-  const int rc = xm_resident_blocks(g_hs_res[FORM], k_hsvd<FORM>, XM_HS_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = A.nb < resident ? A.nb : resident;
-  xm_note_kernel("k_hsvd", nullptr, FORM == XM_HS_FORM_MFMA ? "mfma" : "fma", A.M, A.K);  // <form, M, K>
-  hipLaunchKernelGGL(k_hsvd<FORM>, dim3((unsigned)blocks), dim3(XM_HS_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(g_hs_res[FORM], k_hsvd<FORM>, XM_HS_NT, hs_lds_bytes(A.M, A.K), A.nb, A, st, "k_hsvd",
+                         FORM == XM_HS_FORM_MFMA ? "mfma" : "fma", A.M, A.K);  // <form, M, K>
 }
 }  // namespace
 
@@ -65,6 +58,5 @@ extern "C" int xm_hsvd_rows(const void* x, int64_t row_stride, void* y_or_null, 
 
   DeviceGuard guard(x);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   return (dtype & XM_HSVD_GRAM_FMA) ? hs_launch<XM_HS_FORM_FMA>(A, st) : hs_launch<XM_HS_FORM_MFMA>(A, st);
 }

@@ -16,7 +16,7 @@
 // every step a fused multiply-add.  The rows are rounded once to the data's dtype and stored at the R full-FOV positions.
 // RB is R rounded up to a power of two: the accumulators are a register array of that size, rows past Ra hold zeros.
 #pragma once
-#include "xm_common.h"
+#include "xm_wg.h"
 
 #define XM_SN_MAXC 64
 #define XM_SN_MAXR 16
@@ -356,10 +356,7 @@ __global__ __launch_bounds__(XM_SN_NT, 2) void k_sense_unfold(SenseArgs A) {
   const long long nfull = nred * R;
 
   for (;;) {
-    if (t == 0) L.word[0] = (int)atomicAdd(A.counter, 1u);
-    __syncthreads();
-    const long long v = (long long)(unsigned)L.word[0];
-    __syncthreads();
+    const long long v = wg_next_item(A.counter, (unsigned*)L.word);
     if (v >= A.ngroups) break;
     const long long o = v / nred, p = v - o * nred;
     const int p3 = (int)(p % A.n[2]), p2 = (int)((p / A.n[2]) % A.n[1]), p1 = (int)(p / ((long long)A.n[2] * A.n[1]));
@@ -395,12 +392,5 @@ __global__ __launch_bounds__(XM_SN_NT, 2) void k_sense_unfold(SenseArgs A) {
     }
     __syncthreads();
   }
-  // the last workgroup out leaves the counters at zero
-  if (t == 0) {
-    const unsigned d = atomicAdd(A.counter + 1, 1u);
-    if (d == gridDim.x - 1u) {
-      __hip_atomic_store(A.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  wg_leave(A.counter);
 }

@@ -11,15 +11,8 @@ XmResidency g_sn_res[2][5];  // one residency record per kernel instantiation: d
 
 template <class T, int RB>
 int sn_launch(const SenseArgs& A, XmResidency& res, hipStream_t st) {
-  const size_t lds = sn_lds_bytes(A.C, A.Rtot, RB);
-  int resident = 0;
-  const int rc = xm_resident_blocks(res, k_sense_unfold<T, RB>, XM_SN_NT, lds, &resident, st);
-  if (rc) return rc;
-  const long long blocks = A.ngroups < resident ? A.ngroups : resident;
-  xm_note_kernel("k_sense_unfold", nullptr, sizeof(T) == 8 ? "c128" : "c64", RB, A.C);  // <dtype, RB, coils>
-  hipLaunchKernelGGL((k_sense_unfold<T, RB>), dim3((unsigned)blocks), dim3(XM_SN_NT), lds, st, A);
-  HIP_TRY(hipGetLastError());
-  return XM_OK;
+  return xm_launch_items(res, k_sense_unfold<T, RB>, XM_SN_NT, sn_lds_bytes(A.C, A.Rtot, RB), A.ngroups, A, st,
+                         "k_sense_unfold", sizeof(T) == 8 ? "c128" : "c64", RB, A.C);  // <dtype, RB, coils>
 }
 
 template <class T>
@@ -81,7 +74,6 @@ extern "C" int xm_sense_unfold(const void* a, void* y, const void* sens, const v
 
   DeviceGuard guard(a);
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned), st));
   if (dtype == XM_C128) return sn_dispatch<double>(A, g_sn_res[1], st);
   return sn_dispatch<float>(A, g_sn_res[0], st);
 }
