@@ -99,6 +99,15 @@ def parity_case(name):
     return make_data(no, c, ni, n, seed=1000 + sum(map(ord, name)))
 
 
+SWEEP_COILS = range(1, 65)  # every coil count the kernel accepts
+
+
+def sweep_case(c):
+    """Three voxels of c coils and 65 points, one full staged tile and a ragged one.  Cases of their own: COIL_TOL is
+    pinned to PARITY_CASES."""
+    return make_data(3, c, 1, Q + 1, seed=7000 + c)
+
+
 def random_psd(c, seed):
     """A random Hermitian positive-definite C x C matrix with a condition number of a few tens."""
     rng = np.random.default_rng(seed)

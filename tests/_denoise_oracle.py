@@ -151,25 +151,41 @@ def conditions(a, b):
                 and min(a["margin"].min(), b["margin"].min()) >= MIN_MARGIN)
 
 
+# P -> the same tuple: every patch size the kernel accepts, as a 1-D patch (P,) on a grid (P + 1,) with N = 96, K = 2 --
+# two windows, each voxel's own row at either end and in the middle.  A list of its own: PARITY_CASES is the set whose
+# route gap tests/test_denoise.py pins DENOISE_TOL to.
+SWEEP_CASES = {p: ((p + 1,), (p,), 96, 2, None) for p in range(2, 65)}
+
 _cache = {}
 
 
-def parity_case(name):
-    """(clean, noisy, eigh result, svd result, seed) of a parity case; the seed is the first that meets `conditions`.
-    Computed once per process and shared: do not modify."""
-    if name not in _cache:
-        grid, patch, n, k, n_outer = PARITY_CASES[name]
+def _first_seed(key, case):
+    """(clean, noisy, eigh result, svd result, seed) of `case`; the seed is the first that meets `conditions`.  Computed
+    once per process and shared: do not modify."""
+    if key not in _cache:
+        grid, patch, n, k, n_outer = case
         for seed in range(64):
             clean, x = make_data(grid, n, k, seed, n_outer)
             a, b = (denoise(x, patch, route=rt) for rt in ("eigh", "svd"))
             if conditions(a, b):
                 break
         else:
-            raise AssertionError(f"{name}: no seed below 64 meets the conditions")
+            raise AssertionError(f"{key}: no seed below 64 meets the conditions")
         for arr in (clean, x, *a.values(), *b.values()):
             arr.setflags(write=False)
-        _cache[name] = (clean, x, a, b, seed)
-    return _cache[name]
+        _cache[key] = (clean, x, a, b, seed)
+    return _cache[key]
+
+
+def parity_case(name):
+    """(clean, noisy, eigh result, svd result, seed) of a parity case; the seed is the first that meets `conditions`.
+    Computed once per process and shared: do not modify."""
+    return _first_seed(name, PARITY_CASES[name])
+
+
+def sweep_case(p):
+    """The same for the patch size p of SWEEP_CASES."""
+    return _first_seed(("sweep", p), SWEEP_CASES[p])
 
 
 def units(res, x):

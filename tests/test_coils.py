@@ -38,6 +38,22 @@ def test_routes_agree_and_gap_is_wide(name):
     assert np.all(a["status"] == 0)
 
 
+def test_every_coil_count_of_the_sweep_has_a_wide_gap():
+    """The inputs of tests/test_gpu_coils.py's sweep over C = 1 ... 64: the gap that makes the comparison meaningful, and
+    the oracle's two routes within the bound the kernel is held to."""
+    worst, smallest = (0.0, 0.0, 0.0), 1.0
+    for c in orc.SWEEP_COILS:
+        x = orc.sweep_case(c)
+        assert x.shape == (3, c, 1, orc.Q + 1)
+        a, b = (orc.combine_batch(x, coil_axis=1, route=r) for r in ("eigh", "svd"))
+        gap = (a["lam1"] - a["lam2"]) / a["lam1"]
+        assert np.all(gap >= MIN_GAP) and np.all(a["status"] == 0), (c, gap.min())
+        smallest = min(smallest, float(gap.min()))
+        worst = tuple(max(w, u) for w, u in zip(worst, orc.route_gap_units(a, b)))
+    print("smallest gap", smallest, "routes differ by (y, w, quality)", worst, "units; bound", COIL_TOL)
+    assert max(worst) <= COIL_TOL
+
+
 def test_tolerance_constant_matches_its_tool():
     assert COIL_TOL == pytest.approx(16 * ROUTE_UNITS, abs=0.5)
 

@@ -46,6 +46,21 @@ def test_routes_agree_and_cases_meet_the_conditions(name):
         assert not orc.conditions(*(orc.denoise(xs, patch, route=rt) for rt in ("eigh", "svd")))
 
 
+def test_every_patch_size_of_the_sweep_meets_the_conditions():
+    """The inputs of tests/test_gpu_denoise.py's sweep over P = 2 ... 64: a seed below 64 meets the conditions at every P
+    (orc.sweep_case raises otherwise: none is skipped), and the oracle's two routes agree within DENOISE_TOL."""
+    assert list(orc.SWEEP_CASES) == list(range(2, 65)) and not set(orc.SWEEP_CASES) & set(orc.PARITY_CASES)
+    worst = [0.0, 0.0]
+    for p, (grid, patch, n, k, n_outer) in orc.SWEEP_CASES.items():
+        assert (grid, patch, n, k, n_outer) == ((p + 1,), (p,), 96, 2, None)
+        _, x, a, b, seed = orc.sweep_case(p)
+        assert orc.conditions(a, b) and 0 <= seed < 64, p
+        gy, gs = orc.route_gap(a, b, x)
+        worst = [max(worst[0], gy), max(worst[1], gs)]
+        assert gy <= DENOISE_TOL["y"] and gs <= DENOISE_TOL["sigma"], (p, gy, gs)
+    print("sweep: routes differ by y", worst[0], "units, sigma", worst[1], "; bounds", DENOISE_TOL)
+
+
 def test_parity_cases_cover_the_kernel_paths():
     ps = {int(np.prod(c[1])) for c in orc.PARITY_CASES.values()}
     ns = {c[2] for c in orc.PARITY_CASES.values()}

@@ -71,6 +71,21 @@ def test_plain_fma_gram_agrees_with_the_oracle_too(name):
     _check(got, want, what=f"{name} fma")
 
 
+# ---- 1b. every coil count ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", list(orc.SWEEP_COILS))
+def test_every_coil_count_on_both_gram_forms(c):
+    """Every C the kernel accepts, so every block-row count of the matrix-core Gram map, every padded row inside a block
+    and every entries-per-thread count of the plain-FMA map; the gaps are checked in tests/test_coils.py."""
+    x = orc.sweep_case(c)
+    want = orc.combine_batch(x, coil_axis=1)
+    got = _run(x)
+    assert ("k_coil_combine<mfma" if c >= 8 else "k_coil_combine<fma") in got["kernel"]
+    _check(got, want, what=f"C={c} svd")
+    fma = _run(x, method="svd_fma")
+    assert "k_coil_combine<fma" in fma["kernel"]
+    _check(fma, want, what=f"C={c} svd_fma")
+
+
 # ---- 2. reference -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_ref", [7, 100])
 def test_reference_of_another_length(n_ref):

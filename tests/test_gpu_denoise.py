@@ -94,6 +94,18 @@ def test_matrix_core_and_fma_gram_agree(name):
     _check(a, dict(b, lam=want["lam"]), x, what=f"{name} mfma against fma")
 
 
+@pytest.mark.parametrize("p", list(orc.SWEEP_CASES))
+def test_every_patch_size_on_both_gram_forms(p):
+    """Every P the kernel accepts (orc.SWEEP_CASES, whose conditions are checked in tests/test_denoise.py): every block-row
+    count and padded row of the matrix-core Gram map, every entries-per-thread count of the plain-FMA one, and every
+    round-robin schedule of the Jacobi with all its eigenvectors in use."""
+    _, x, want, _, _ = orc.sweep_case(p)
+    a, b = _run(x, (p,)), _run(x, (p,), _gram_fma=True)
+    assert f"k_denoise<{'mfma' if p >= 8 else 'fma'}, {p}>" in a["kernel"] and "k_denoise<fma" in b["kernel"]
+    _check(a, want, x, what=f"P={p}")
+    _check(b, want, x, what=f"P={p} fma")
+
+
 # ---- 1b. scale ------------------------------------------------------------------------------------------------------------
 def _scaled(x, e):
     if x.dtype == np.complex64:

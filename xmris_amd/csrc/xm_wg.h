@@ -291,12 +291,13 @@ XM_DEV int wg_jacobi(double* G, double* V, double* red, double* rot, int C) {
 enum { XM_WG_FIXED = 0, XM_WG_FREE = 1, XM_WG_LO = 2, XM_WG_HI = 3, XM_WG_TWO = 4 };
 
 // physical value and dp/du of a parameter from its internal value (lmfit's transforms).  A two-sided parameter at
-// sin u = +-1 (on a bound) has slope exactly 0: it stays where it is.
+// sin u = +-1 (on a bound) has slope exactly 0: it stays where it is, and its value is the bound itself (the formula's
+// lo + (hi - lo) need not round to hi: lo = -1e6, hi = 1e-6 gives 1.0000076e-6, a value outside the bounds).
 XM_DEV void wg_from_internal(int bt, double u, double lo, double hi, double& p, double& s) {
   if (bt == XM_WG_TWO) {
     double sn, cs;
     sincos(u, &sn, &cs);
-    p = lo + (sn + 1.0) * (hi - lo) * 0.5;
+    p = sn == 1.0 ? hi : lo + (sn + 1.0) * (hi - lo) * 0.5;
     s = (sn == 1.0 || sn == -1.0) ? 0.0 : cs * (hi - lo) * 0.5;
   } else if (bt == XM_WG_LO) {
     const double r = sqrt(u * u + 1.0);
