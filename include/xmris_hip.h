@@ -444,6 +444,23 @@ int xm_sense_unfold(const void* a, void* y, const void* sens, const void* linv_o
 int xm_axis_sparse(const void* x, void* y, const int32_t* rowptr, const int32_t* col, const double* val, int64_t n_outer,
                    int64_t n, int64_t n_rows, int64_t n_inner, int dtype, void* stream);
 
+/* ---- Per-row time shift of FIDs (this backend's own definition, the reference has none).
+ * `in`: n_rows rows of n points, `in_row_stride` elements apart; `out`: n_rows contiguous rows of n points.  Row r is
+ * delayed by phi = frac[(r / delay_div) % n_delay] dwells (`frac`: n_delay fp64 in device memory):
+ *   X[k] = sum_{j<n} in[r][j] e^{-2 pi i k j / L},  out[r][j] = (1/L) sum_{k<L} X[k] e^{-2 pi i kappa_k phi / L} e^{+2 pi i k j / L},
+ * kappa_k = k for k < L/2 and k - L from there on (numpy.fft.fftfreq(L) L; the Nyquist bin is -L/2).  One launch of
+ * k_shift_time: load, transform, ramp, transform back, store.  The ramp is formed in fp64 with kappa_k phi / L reduced
+ * modulo 1 on the integer part of phi and rounded once to `dtype` (XM_C64 / XM_C128); the transforms run in `dtype`.
+ * A row depends on its own samples and delay only, and a zero delay takes the same arithmetic as any other.
+ * xm_shift_time_fused(L, dtype) is 1 for the lengths that have the kernel -- the direct in-LDS plans; 16384 in
+ * complex64 only -- and 0 otherwise: callers compose those from xm_zero_fill, xm_fft1d_batched and a phase product.
+ * 1 <= n <= L, L in the fused set, n_rows >= 0 (at most 2^31 - 1), in_row_stride >= n, n_delay >= 1, delay_div >= 1,
+ * non-NULL pointers aligned to their element size, out != in and a known dtype: otherwise XM_ERR_INVALID_ARG before
+ * any HIP call, and nothing is written.  n_rows = 0 launches nothing. */
+int xm_shift_time_fused(int L, int dtype);
+int xm_shift_time(const void* in, int64_t in_row_stride, void* out, int64_t n_rows, int n, int L, const double* frac,
+                  int64_t n_delay, int64_t delay_div, int dtype, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

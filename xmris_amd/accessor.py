@@ -142,38 +142,54 @@ class XmrisMrsiMixin:
         return to_kspace(self._obj, dim=dim, out_dim=out_dim, matrix=matrix, filter=filter, shift=shift)
 
     def grid_kspace(self, trajectory, matrix, oversampling: float = 2.0, width: int = 4, density=None,
-                    dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = 10):
+                    dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = 10, readout_time=None):
         """Non-Cartesian samples to the oversampled Cartesian k-space, one launch of the gather kernel (an addition of
         this backend)."""
         from .processing.grid import grid_kspace
 
         return grid_kspace(self._obj, trajectory, matrix, oversampling=oversampling, width=width, density=density,
-                           dim=dim, out_dim=out_dim, fov=fov, iterations=iterations)
+                           dim=dim, out_dim=out_dim, fov=fov, iterations=iterations, readout_time=readout_time)
 
     def degrid_kspace(self, trajectory, matrix, oversampling: float = 2.0, width: int = 4, dim=None,
-                      out_dim: str = DIMS.sample):
+                      out_dim: str = DIMS.sample, readout_time=None):
         """The oversampled Cartesian k-space at a trajectory's samples: the transpose of ``grid_kspace`` (DESIGN.md
         section 17)."""
         from .processing.grid import degrid_kspace
 
-        return degrid_kspace(self._obj, trajectory, matrix, oversampling=oversampling, width=width, dim=dim, out_dim=out_dim)
+        return degrid_kspace(self._obj, trajectory, matrix, oversampling=oversampling, width=width, dim=dim, out_dim=out_dim,
+                             readout_time=readout_time)
 
     def nufft_adjoint(self, trajectory, matrix, oversampling: float = 2.0, width: int = 4, density=None,
-                      dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = 10):
+                      dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = 10, readout_time=None):
         """Non-Cartesian samples to voxels: gridding, centred inverse transform, crop and de-apodisation (DESIGN.md
         section 17)."""
         from .processing.grid import nufft_adjoint
 
         return nufft_adjoint(self._obj, trajectory, matrix, oversampling=oversampling, width=width, density=density,
-                             dim=dim, out_dim=out_dim, fov=fov, iterations=iterations)
+                             dim=dim, out_dim=out_dim, fov=fov, iterations=iterations, readout_time=readout_time)
 
     def nufft_forward(self, trajectory, matrix=None, oversampling: float = 2.0, width: int = 4, dim=None,
-                      out_dim: str = DIMS.sample):
+                      out_dim: str = DIMS.sample, readout_time=None):
         """Voxels to non-Cartesian samples: the transpose chain of ``nufft_adjoint``."""
         from .processing.grid import nufft_forward
 
         return nufft_forward(self._obj, trajectory, matrix=matrix, oversampling=oversampling, width=width, dim=dim,
-                             out_dim=out_dim)
+                             out_dim=out_dim, readout_time=readout_time)
+
+    def shift_time(self, delay, dim: str = DIMS.time, pad_to=None, dwell=None):
+        """Each row along `dim` evaluated `delay` earlier, one fused launch (an addition of this backend; DESIGN.md
+        section 18)."""
+        from .processing.timeshift import shift_time
+
+        return shift_time(self._obj, delay, dim=dim, pad_to=pad_to, dwell=dwell)
+
+    def correct_readout_time(self, offsets, dim: str = DIMS.time, sample_dim: str = DIMS.sample, pad_to=None, dwell=None,
+                             inverse: bool = False):
+        """Undo the acquisition delay of each sample of a non-Cartesian readout."""
+        from .processing.timeshift import correct_readout_time
+
+        return correct_readout_time(self._obj, offsets, dim=dim, sample_dim=sample_dim, pad_to=pad_to, dwell=dwell,
+                                    inverse=inverse)
 
     def unfold_sense(self, sensitivities, accel, dims=(DIMS.x, DIMS.y), coil_dim: str = DIMS.coil,
                      time_dim: str = DIMS.time, noise_cov=None, regularization: float = 0.0, return_maps: bool = False):

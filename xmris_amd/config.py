@@ -76,6 +76,8 @@ class _Attrs(_Vocabulary):
     grid_width = XmrisTerm("grid_width", "Width of the Kaiser-Bessel gridding kernel.", "grid cells")
     grid_beta = XmrisTerm("grid_beta", "Shape parameter of the Kaiser-Bessel gridding kernel along each gridded dimension.")
     grid_density = XmrisTerm("grid_density", "Density compensation of the gridding: 'none', 'pipe' or 'custom'.")
+    time_shift_pad_to = XmrisTerm("time_shift_pad_to", "Transform length of the last time shift along the FID axis.")
+    readout_time_corrected = XmrisTerm("readout_time_corrected", "Whether the acquisition delays of the readout's samples have been removed.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 

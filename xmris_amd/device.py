@@ -984,6 +984,67 @@ def axis_sparse(x, axis: int, table: SparseTable):
     return out
 
 
+def shift_time_fused(L: int, complex128: bool = False) -> bool:
+    """True when `shift_time` runs transform length `L` as one launch of k_shift_time (`xm_shift_time_fused`)."""
+    return bool(_lib.load().xm_shift_time_fused(int(L), _lib.XM_C128 if complex128 else _lib.XM_C64))
+
+
+def _shift_ramp(frac, L: int):
+    """exp(-2 pi i kappa_k phi / L) for each phi of `frac` (fp64 device tensor) -> [len(frac), L] complex128: the staged
+    route's ramp, with kappa phi / L reduced modulo 1 on the integer part of phi as the kernel does (every product below
+    is an exact integer in fp64)."""
+    torch = _torch()
+    k = torch.arange(L, dtype=torch.float64, device=frac.device)
+    kappa = torch.where(k < (L + 1) // 2, k, k - L)
+    whole = torch.round(frac)
+    part = frac - whole
+    m = torch.remainder(kappa[None, :] * torch.remainder(whole, L)[:, None], L)
+    angle = (-2.0 * np.pi) * ((m + kappa[None, :] * part[:, None]) / L)
+    return torch.complex(torch.cos(angle), torch.sin(angle))
+
+
+def shift_time(x, axis: int, frac, n_delay: int | None = None, delay_div: int = 1, L: int | None = None,
+               staged: bool = False):
+    """Each row of `x` along `axis` delayed by its own number of dwells (`xm_shift_time`): with
+    `axis` moved last and the rest flattened, row r takes ``frac[(r // delay_div) % n_delay]``; `frac` holds `n_delay`
+    fp64 values (host values or a device tensor), `L` >= the axis length is the transform length (default: the axis
+    length).  One launch of k_shift_time where `shift_time_fused(L)`; any other length -- chirp-z lengths, lengths above
+    16384, complex128 16384 -- and `staged=True` take the same definition in stages: zero fill, transform, the ramp
+    (built in fp64 on the device), inverse transform, crop.  Returns a new tensor of x's shape; `x` is left untouched."""
+    _require_device(x)
+    torch = _torch()
+    code = _dtype_code(x)
+    x2, restore = _rows(x, axis)
+    nb, n = x2.shape
+    L = n if L is None else int(L)
+    if L < n:
+        raise ValueError(f"L: the transform length {L} is shorter than the axis ({n} points)")
+    if isinstance(frac, torch.Tensor):
+        fr = frac.to(device=x.device, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        fr = torch.from_numpy(np.array(frac, dtype=np.float64).reshape(-1)).to(x.device)
+    n_delay = fr.numel() if n_delay is None else int(n_delay)
+    delay_div = int(delay_div)
+    if n_delay < 1 or n_delay != fr.numel() or delay_div < 1:
+        raise ValueError(f"frac: {fr.numel()} delays for n_delay = {n_delay}, delay_div = {delay_div}")
+    if nb == 0 or n == 0:
+        return restore(torch.empty_like(x2))
+    if not staged and shift_time_fused(L, x.dtype == torch.complex128):
+        out = torch.empty_like(x2)
+        _lib.call("xm_shift_time", x2.data_ptr(), n, out.data_ptr(), nb, n, L, fr.data_ptr(), n_delay, delay_div, code,
+                  _stream(x))
+        return restore(out)
+    spec = fft(zero_fill(x2, 1, L) if L > n else x2, 1, inverse=False, ortho=False)
+    ramp = _shift_ramp(fr, L).to(x.dtype)  # rounded once to the storage precision
+    period = n_delay * delay_div
+    if nb % period == 0:
+        spec.view(nb // period, n_delay, delay_div, L).mul_(ramp[None, :, None, :])
+    else:
+        spec.mul_(ramp[(torch.arange(nb, device=x.device) // delay_div) % n_delay])
+    y = fft(spec, 1, inverse=True, ortho=False)
+    return restore(y[:, :n].contiguous() if L > n else y)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 

@@ -3,7 +3,8 @@ front of ``to_image`` for spiral, radial, concentric-ring, rosette and ramp-samp
 
 The definition is this backend's own (the reference has nothing here).  `trajectory` is [S, d]
 real, d = 1 ... 3, in cycles per field of view, k in [-m/2, m/2] per dim for the target matrix m; it is the same for
-every time point and every other dim (per-sample time offsets within a readout are not corrected).  Per dim:
+every time point and every other dim (per-sample time offsets within a readout: the keyword `readout_time`,
+``processing/timeshift.py``).  Per dim:
 
     G = the smallest even integer >= oversampling m,  alpha = G / m,  W = width <= G
     beta = pi sqrt((W / alpha)^2 (alpha - 1/2)^2 - 0.8)                                   (Beatty et al. 2005)
@@ -210,6 +211,15 @@ def _attrs(src, names, t: GridTable, label: str):
     return attrs
 
 
+def _readout(da, readout_time, sample_dim: str, inverse: bool):
+    """`da` itself for ``readout_time=None``; otherwise ``correct_readout_time`` along the ``time`` dim."""
+    if readout_time is None:
+        return da
+    from .timeshift import correct_readout_time
+
+    return correct_readout_time(da, readout_time, sample_dim=sample_dim, inverse=inverse)
+
+
 def _grid(da, trajectory, matrix, oversampling, width, density, iterations, dim, out_dim, fov, name):
     """Validation, table and the gridding launch: (source, tensor with the flat cell axis, axis, names, table, fov)."""
     src = as_labeled(da)
@@ -238,13 +248,15 @@ def _expand(src, dim, names, coords_of):
 
 
 def grid_kspace(da, trajectory, matrix, oversampling: float = 2.0, width: int = 4, density=None, dim: str = DIMS.sample,
-                out_dim=None, fov=1.0, iterations: int = PIPE_ITERATIONS):
+                out_dim=None, fov=1.0, iterations: int = PIPE_ITERATIONS, readout_time=None):
     """Non-Cartesian samples -> the oversampled Cartesian k-space: one launch of the gather kernel for all coils and time
     points (module docstring).  `trajectory`: [S, d] in cycles per field of view; `matrix`: the target matrix m (an int
     or one per dim); `density`: None, S real weights or ``"pipe"`` (`iterations` rounds of Pipe-Menon).  The `dim` dim
     is replaced in place by ``kx[, ky[, kz]]`` (or `out_dim`) of G points each with the coordinate
     ``(arange(G) - G // 2) (m / G) / fov``; other coords and attrs are kept, ``grid_*`` attrs are added; the result is
-    device-resident for LabeledArray input.  A cell that no sample touches is zero."""
+    device-resident for LabeledArray input.  A cell that no sample touches is zero.  `readout_time`: None, or the S
+    acquisition delays of the samples in the unit of the ``time`` coordinate: ``correct_readout_time`` runs first."""
+    da = _readout(da, readout_time, dim, False)
     src, y, axis, names, t, f = _grid(da, trajectory, matrix, oversampling, width, density, iterations, dim, out_dim, fov,
                                       "grid_kspace")
     shape = tuple(y.shape)
@@ -268,12 +280,13 @@ def _narrow(x, axis: int, start: int, length: int):
 
 
 def nufft_adjoint(da, trajectory, matrix, oversampling: float = 2.0, width: int = 4, density=None,
-                  dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = PIPE_ITERATIONS):
+                  dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = PIPE_ITERATIONS, readout_time=None):
     """Non-Cartesian samples -> voxels: ``grid_kspace``, then per dim the centred inverse transform, the crop to
     `matrix` and the de-apodisation in one launch (module docstring).  Approximates
     ``(1 / sqrt(m^d)) sum_j dens_j x_j exp(2 pi i k_j (p - m // 2) / m)``; for a full Cartesian trajectory with unit
     density that is ``to_image``.  The `dim` dim is replaced in place by ``x[, y[, z]]`` (or `out_dim`) of m points each
-    with the coordinate ``(arange(m) - m // 2) fov / m``."""
+    with the coordinate ``(arange(m) - m // 2) fov / m``.  `readout_time`: as in ``grid_kspace``."""
+    da = _readout(da, readout_time, dim, False)
     src, y, axis, names, t, f = _grid(da, trajectory, matrix, oversampling, width, density, iterations, dim, out_dim, fov,
                                       "nufft_adjoint")
     shape = tuple(y.shape)
@@ -342,22 +355,26 @@ def _apply_degrid(x, axis: int, t: GridTable):
     return dev.axis_sparse(flat, axis, t.degrid)
 
 
-def degrid_kspace(da, trajectory, matrix, oversampling: float = 2.0, width: int = 4, dim=None, out_dim: str = DIMS.sample):
+def degrid_kspace(da, trajectory, matrix, oversampling: float = 2.0, width: int = 4, dim=None, out_dim: str = DIMS.sample,
+                  readout_time=None):
     """The oversampled Cartesian k-space -> its values at the trajectory's samples: the transpose of ``grid_kspace``
     with unit density, one launch.  `dim`: the k-space dims in the trajectory's order (``kx[, ky[, kz]]`` by default),
-    of G points each; they are replaced by `out_dim` (S points, coordinate ``arange(S)``) at the place of the first."""
+    of G points each; they are replaced by `out_dim` (S points, coordinate ``arange(S)``) at the place of the first.
+    `readout_time`: None, or the S acquisition delays of the samples: ``correct_readout_time(inverse=True)`` runs last,
+    the transpose of what ``grid_kspace`` does with them."""
     src, x, axis, names, t = _degrid(da, trajectory, matrix, oversampling, width, dim, out_dim, K_DIMS, "degrid_kspace", False)
     y = _apply_degrid(x, axis, t)
     dims, coords = _collapse(src, names, out_dim, t.grid.n)
-    return like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, "none"), src.name), da)
+    return _readout(like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, "none"), src.name), da), readout_time,
+                    out_dim, True)
 
 
 def nufft_forward(da, trajectory, matrix=None, oversampling: float = 2.0, width: int = 4, dim=None,
-                  out_dim: str = DIMS.sample):
+                  out_dim: str = DIMS.sample, readout_time=None):
     """Voxels -> non-Cartesian samples: the transpose chain of ``nufft_adjoint`` with unit density (the product with c,
     the centred forward transform zero filled to G, degridding); with ``nufft_adjoint`` the building blocks of an
     iterative reconstruction.  `dim`: the image dims in the trajectory's order (``x[, y[, z]]`` by default); `matrix`
-    defaults to their sizes."""
+    defaults to their sizes.  `readout_time`: as in ``degrid_kspace``."""
     src0 = as_labeled(da)
     k = _trajectory(trajectory)
     names = X_DIMS[:k.shape[1]] if dim is None else ((dim,) if isinstance(dim, str) else tuple(dim))
@@ -376,4 +393,5 @@ def nufft_forward(da, trajectory, matrix=None, oversampling: float = 2.0, width:
             x = dev.fft(x, axis + a, inverse=False, ortho=True, shift_in=True, shift_out=True)
     y = _apply_degrid(x, axis, t)
     dims, coords = _collapse(src, names, out_dim, t.grid.n)
-    return like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, "none"), src.name), da)
+    return _readout(like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, "none"), src.name), da), readout_time,
+                    out_dim, True)
