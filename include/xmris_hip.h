@@ -461,6 +461,35 @@ int xm_shift_time_fused(int L, int dtype);
 int xm_shift_time(const void* in, int64_t in_row_stride, void* out, int64_t n_rows, int n, int L, const double* frac,
                   int64_t n_delay, int64_t delay_div, int dtype, void* stream);
 
+/* ---- Per-voxel rate fitting of a dynamic series (this backend's own definition, the reference
+ * has none).  One substrate and M = n_products products over T = n_times repetitions at times[T] (HOST, seconds,
+ * increasing), flip angles flip_s[T] and flip_p[M, T] (HOST, radians, inside (0, pi / 2)).  Device arrays, fp64:
+ * substrate [n_batch, T], products and weights [n_batch, M, T] (weights NULL: all 1; a point of weight 0 is missing
+ * and its sample is not read).  Each (voxel, product) pair is one fit of k [1/s], rho [1/s] and z:
+ *   Zs_n = S_n / sin flip_s[n],  Zs+_n = Zs_n cos flip_s[n],  D_n = times[n+1] - times[n],  x = rho D_n
+ *   Z_0 = z,  Z_{n+1} = e^{-x} cos flip_p[m, n] Z_n + k (w0_n Zs+_n + w1_n Zs_{n+1}),
+ *   w1_n = D_n (x - 1 + e^{-x}) / x^2,  w0_n = D_n (1 - e^{-x}) / x - w1_n,  P^_n = Z_n sin flip_p[m, n],
+ *   cost = sum_n weights[n]^2 (P_n - P^_n)^2,
+ * by Levenberg-Marquardt in lmfit's bound variables, the iteration and the stopping rules of xm_basis_fit, one wave
+ * per fit (k_kinetics_fit).  init / lower / upper / fixed: HOST [M, 3] in the order k, rho, z, shared by the batch; a
+ * parameter is fixed when flagged or when lower == upper.  A free k or rho needs two finite bounds; z any.  A NaN
+ * init of a free z starts it per fit at |P_j| / sin flip_p[m, j], j the first repetition of positive weight.
+ * Outputs: params and param_sd [n_batch, M, 3]; rss, status, iters, auc_ratio [n_batch, M]; fit [n_batch, M, T] (the
+ * model at every repetition; may be NULL).  status: 0 converged, 1 iteration cap, 2 non-finite, 3 fewer points of
+ * positive weight (T_w) than free parameters (P); for 2 and 3 every output of the fit is 0 and rss is NaN.
+ * param_sd: sqrt(diag((J^T W J)^{-1}) rss / (T_w - P)) over the physical free parameters, 0 for a fixed one, NaN when
+ * the matrix is singular or T_w = P.  auc_ratio: the trapezoid area over `times` of P_m divided by that of S, both over
+ * the points of positive weight.
+ * XM_ERR_INVALID_ARG before any HIP call, nothing written: T outside 2 ... 256, M outside 1 ... 8, n_batch < 0, times
+ * not finite or not increasing, a flip angle outside (0, pi / 2), a NaN bound or lower > upper, an infinite bound of a
+ * free k or rho, a negative lower bound of rho, a non-finite init (but the NaN of z), every parameter of a product
+ * fixed, max_iter < 1, a negative or NaN tolerance, a null pointer (but weights and fit).  n_batch = 0 returns 0. */
+int xm_kinetics_fit(const double* substrate, const double* products, const double* weights, int64_t n_batch,
+                    int n_products, int n_times, const double* times, const double* flip_s, const double* flip_p,
+                    const double* init, const double* lower, const double* upper, const int32_t* fixed, int max_iter,
+                    double ftol, double xtol, double* params, double* param_sd, double* rss, int32_t* status,
+                    int32_t* iters, double* fit, double* auc_ratio, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

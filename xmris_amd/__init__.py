@@ -10,7 +10,7 @@ __version__ = "0.4.0"
 from . import _lib  # noqa: F401
 from .accessor import XmrisAccessor, register_xarray_accessor
 from .config import ATTRS, COORDS, DIMS
-from .fitting import basis_model, fit_amares, fit_basis, simulate_fid
+from .fitting import basis_model, fit_amares, fit_basis, fit_kinetics, simulate_fid, simulate_kinetics
 from .fused import spectral_pipeline
 from .labeled import Coordinate, LabeledArray
 from .vendor.bruker import remove_digital_filter
@@ -25,4 +25,4 @@ __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "
            "apodize_exp", "apodize_lg", "autophase", "autophase_each", "basis_model", "fft", "fit_amares", "fit_basis", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
            "phase", "register_xarray_accessor", "remove_digital_filter", "remove_water", "sense_maps", "simulate_fid", "spectral_pipeline", "to_fid", "to_image", "to_kspace", "to_spectrum", "unfold_sense", "zero_fill",
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table",
-           "shift_time", "correct_readout_time", "readout_offsets"]
+           "shift_time", "correct_readout_time", "readout_offsets", "fit_kinetics", "simulate_kinetics"]

@@ -98,7 +98,9 @@ SIGNATURES = {
     "xm_axis_sparse": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _p]),
     "xm_shift_time_fused": (_i, [_i, _i]),
     "xm_shift_time": (_i, [_p, _l, _p, _l, _i, _i, _p, _l, _l, _i, _p]),
-    "xm_gather_row_c128": (_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
+    "xm_kinetics_fit": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, ctypes.c_double, ctypes.c_double, _p, _p,
+                             _p, _p, _p, _p, _p, _p]),
+    "xm_gather_row_c128":(_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_ramp_native": (_i, [_p, _l, _i, _i, _i, _u, _i]),

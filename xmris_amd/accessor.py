@@ -224,6 +224,17 @@ class XmrisFittingMixin:
                          max_gaussian=max_gaussian, gaussian_start=gaussian_start, fit_phase=fit_phase, skip=skip,
                          amplitude_start=amplitude_start, max_iter=max_iter, return_fit=return_fit)
 
+    def fit_kinetics(self, substrate, products, dim: str = "repetition", times=None, flip_angle=None,
+                     r1=(1.0 / 60.0, 1.0 / 10.0), rate_bounds=(0.0, 1.0), fit_initial: bool = False, sigma=None,
+                     metabolite_dim: str = "Metabolite", max_iter: int = 200):
+        """Per-voxel conversion rates of a dynamic series of amplitudes (an addition of this backend; DESIGN.md
+        section 19)."""
+        from .fitting.kinetics import fit_kinetics
+
+        return fit_kinetics(self._obj, substrate, products, dim=dim, times=times, flip_angle=flip_angle, r1=r1,
+                            rate_bounds=rate_bounds, fit_initial=fit_initial, sigma=sigma, metabolite_dim=metabolite_dim,
+                            max_iter=max_iter)
+
 
 class XmrisAccessor(XmrisFourierMixin, XmrisProcessingMixin, XmrisPhasingMixin, XmrisVendorMixin, XmrisFusedMixin,
                     XmrisFittingMixin, XmrisMrsiMixin):

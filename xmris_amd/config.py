@@ -78,6 +78,13 @@ class _Attrs(_Vocabulary):
     grid_density = XmrisTerm("grid_density", "Density compensation of the gridding: 'none', 'pipe' or 'custom'.")
     time_shift_pad_to = XmrisTerm("time_shift_pad_to", "Transform length of the last time shift along the FID axis.")
     readout_time_corrected = XmrisTerm("readout_time_corrected", "Whether the acquisition delays of the readout's samples have been removed.")
+    kinetics_model = XmrisTerm("kinetics_model", "Rate model that fit_kinetics fitted along the repetitions.")
+    kinetics_substrate = XmrisTerm("kinetics_substrate", "Name of the metabolite whose measured amplitudes drive the rate model.")
+    kinetics_dim = XmrisTerm("kinetics_dim", "Name of the repetition dimension the rates were fitted along.")
+    kinetics_flip_angle = XmrisTerm("kinetics_flip_angle", "Flip angle of each metabolite of the rate model at every repetition.", "degrees")
+    kinetics_rate_bounds = XmrisTerm("kinetics_rate_bounds", "Bounds of the fitted conversion rate.", "1/s")
+    kinetics_decay_bounds = XmrisTerm("kinetics_decay_bounds", "Bounds of each product's effective decay rate (equal: fixed).", "1/s")
+    kinetics_fit_initial = XmrisTerm("kinetics_fit_initial", "Whether the products' magnetisation before the first excitation was fitted.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 

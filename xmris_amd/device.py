@@ -477,6 +477,60 @@ def basis_fit(x, axis: int, basis, group, init, lo, hi, fixed, dt: float, skip: 
                     fit=fit.reshape(lead + (n,)) if fit is not None else None, n_free=n_free)
 
 
+class KineticsFit:
+    """Raw outputs of ``kinetics_fit``: params and param_sd [n_batch, M, 3] (k, rho, z), rss, status (0 converged,
+    1 iteration cap, 2 non-finite, 3 fewer weighted points than free parameters), iters and auc_ratio [n_batch, M],
+    fit [n_batch, M, T] (or None); n_free [M]: the free parameters of each product."""
+
+    __slots__ = ("params", "param_sd", "rss", "status", "iters", "fit", "auc_ratio", "n_free")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def kinetics_fit(substrate, products, times, flip_s, flip_p, init, lo, hi, fixed, weights=None, max_iter: int = 200,
+                 ftol: float = 1e-10, xtol: float = 1e-10, want_fit: bool = True) -> KineticsFit:
+    """One rate fit per (voxel, product) pair, all in one launch of k_kinetics_fit (xm_kinetics_fit, DESIGN.md section
+    19).  Device tensors: substrate [n_batch, T], products and weights [n_batch, M, T] (weights None: all 1; a point of
+    weight 0 is missing).  Host values: times [T] (seconds), flip_s [T] and flip_p [M, T] (radians), init / lo / hi /
+    fixed [M, 3] in the order k, rho, z, shared by every voxel (a NaN start of a free z: the automatic per-fit start)."""
+    torch = _torch()
+    _require_device(substrate)
+    _require_device(products)
+    s = substrate.to(torch.float64).contiguous()
+    y = products.to(torch.float64).contiguous()
+    if s.dim() != 2 or y.dim() != 3 or y.shape[0] != s.shape[0] or y.shape[2] != s.shape[1]:
+        raise ValueError(f"kinetics_fit needs substrate [n_batch, T] and products [n_batch, M, T], got {tuple(s.shape)} "
+                         f"and {tuple(y.shape)}")
+    nb, m, t = y.shape
+    w = None
+    if weights is not None:
+        _require_device(weights)
+        w = weights.to(torch.float64).contiguous()
+        if tuple(w.shape) != (nb, m, t):
+            raise ValueError(f"weights must have the products' shape {(nb, m, t)}, got {tuple(w.shape)}")
+    host = lambda v, shape: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape))  # noqa: E731
+    times, flip_s, flip_p = host(np.asarray(times).reshape(-1), (t,)), host(flip_s, (t,)), host(flip_p, (m, t))
+    init, lo, hi = (host(v, (m, 3)) for v in (init, lo, hi))
+    fixed = np.ascontiguousarray(np.broadcast_to(np.asarray(fixed, dtype=bool), (m, 3)).astype(np.int32))
+    dev_ = s.device
+    f64 = dict(dtype=torch.float64, device=dev_)
+    params, psd = torch.empty((nb, m, 3), **f64), torch.empty((nb, m, 3), **f64)
+    rss, auc = torch.empty((nb, m), **f64), torch.empty((nb, m), **f64)
+    status = torch.empty((nb, m), dtype=torch.int32, device=dev_)
+    iters = torch.empty((nb, m), dtype=torch.int32, device=dev_)
+    fit = torch.empty((nb, m, t), **f64) if want_fit else None
+    ptr = lambda a: a.ctypes.data  # noqa: E731  (host arrays)
+    _lib.call("xm_kinetics_fit", s.data_ptr(), y.data_ptr(), w.data_ptr() if w is not None else None, nb, m, t,
+              ptr(times), ptr(flip_s), ptr(flip_p), ptr(init), ptr(lo), ptr(hi), ptr(fixed), int(max_iter), float(ftol),
+              float(xtol), params.data_ptr(), psd.data_ptr(), rss.data_ptr(), status.data_ptr(), iters.data_ptr(),
+              fit.data_ptr() if fit is not None else None, auc.data_ptr(), _stream(s))
+    n_free = np.count_nonzero(~(fixed.astype(bool) | (lo == hi)), axis=1)
+    return KineticsFit(params=params, param_sd=psd, rss=rss, status=status, iters=iters, fit=fit, auc_ratio=auc,
+                       n_free=n_free)
+
+
 class CoilCombine:
     """Raw outputs of ``coil_combine`` with the axes of the input other than coil and time in front, in the input's
     order: y [..., N] (the input's dtype), weights [..., C] complex128, quality [...] fp64, status [...] int32
