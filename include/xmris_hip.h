@@ -429,6 +429,28 @@ int xm_sense_unfold(const void* a, void* y, const void* sens, const void* linv_o
                     const int64_t a_strides[5], const int64_t y_strides[4], double regularization, int dtype,
                     void* workspace, void* stream);
 
+/* ---- GRAPPA fill of regularly undersampled Cartesian MRSI (this backend's own definition, the
+ * reference has none).  `a`: the kept k-space lines of C coils, n[0] x n[1] x n[2] lines (an unused dim has n = accel =
+ * kernel = 1) and N_t time points; `y`: the full grid, N_d = accel[d] n[d] lines per dim, the dtype of `a`.  `a_strides`,
+ * `y_strides`: element strides of the outer axis, the coil axis and the three spatial axes; time is contiguous and last
+ * in both.  Per dim the kept lines of the full centred k-space are j = j0 + accel l, j0 = N / 2 - accel (n / 2).  A full
+ * position j has l = floor((j - j0) / accel) (-1 below j0) and o = (j - j0) mod accel >= 0 per dim.  o = 0 in every dim:
+ * the position is acquired and copied bit for bit.  Any other offset tuple is a type tau = ((o_0 accel[1] + o_1)
+ * accel[2] + o_2) - 1, and with b = kernel, S = b_0 b_1 b_2,
+ *   y[c, j, t] = sum_s sum_c' W[tau][c][s][c'] a[c', l + s, t],   s_d = -((b_d - 1) / 2) ... b_d / 2,
+ * s row-major over (s_0, s_1, s_2); a neighbour outside 0 ... n_d - 1 is skipped.  The sum runs in ascending s, then
+ * ascending c', in fp64, every step a fused multiply-add (complex64 samples are widened on load), and is rounded once to
+ * `dtype` (XM_C64 / XM_C128).  `weights`: [R - 1][C][S][C] complex128, contiguous, in device memory, R = accel[0]
+ * accel[1] accel[2]; NULL only when R = 1 (the call is then a copy).  One launch of a plain grid writes every element
+ * of y exactly once; an output depends on its own sources only, so results are bitwise independent of the batch and of
+ * the layout, and a non-finite sample reaches exactly the outputs whose source set holds it.  Non-NULL pointers,
+ * 1 <= C <= 64, accel >= 1, R <= 16, kernel >= 1, S <= 64, C S <= 1024, n >= 1, N_t >= 1, n_outer >= 0, y != a, a known
+ * dtype, and at most 2^31 - 2^16 work items (n_outer x positions x coil blocks x time tiles): otherwise
+ * XM_ERR_INVALID_ARG before any HIP call, with nothing written.  n_outer = 0 launches nothing. */
+int xm_grappa_fill(const void* a, void* y, const void* weights, int64_t n_outer, int C, const int32_t n[3],
+                   const int32_t accel[3], const int32_t kernel[3], int N_t, const int64_t a_strides[5],
+                   const int64_t y_strides[5], int dtype, void* stream);
+
 /* ---- Non-Cartesian gridding: a sparse real matrix along one axis (this backend's own definition,
  * the reference has none).  x is viewed as (n_outer, n, n_inner) and y as (n_outer, n_rows, n_inner), both C-contiguous:
  * any axis of a contiguous tensor is such a view, so nothing is transposed.  The matrix is in CSR form in device memory:

@@ -95,6 +95,7 @@ SIGNATURES = {
     "xm_denoise_patches": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "xm_axis_dft": (_i, [_p, _p, _p, _l, _i, _i, _l, _i, _p]),
     "xm_sense_unfold": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _i, _p, _p, ctypes.c_double, _i, _p, _p]),
+    "xm_grappa_fill": (_i, [_p, _p, _p, _l, _i, _p, _p, _p, _i, _p, _p, _i, _p]),
     "xm_axis_sparse": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _p]),
     "xm_shift_time_fused": (_i, [_i, _i]),
     "xm_shift_time": (_i, [_p, _l, _p, _l, _i, _i, _p, _l, _l, _i, _p]),

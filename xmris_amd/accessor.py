@@ -200,6 +200,17 @@ class XmrisMrsiMixin:
         return unfold_sense(self._obj, sensitivities, accel, dims=dims, coil_dim=coil_dim, time_dim=time_dim,
                             noise_cov=noise_cov, regularization=regularization, return_maps=return_maps)
 
+    def grappa_fill(self, weights=None, *, acs=None, accel=None, kernel=None, dims=None, coil_dim: str = DIMS.coil,
+                    time_dim: str = DIMS.time, acs_points: int = 8, regularization: float = 1e-4,
+                    return_weights: bool = False):
+        """GRAPPA fill of a regularly undersampled k-space to the full grid, the weights given or calibrated from a
+        fully sampled centre block, one launch (an addition of this backend)."""
+        from .processing.grappa import grappa_fill
+
+        return grappa_fill(self._obj, weights, acs=acs, accel=accel, kernel=kernel, dims=dims, coil_dim=coil_dim,
+                           time_dim=time_dim, acs_points=acs_points, regularization=regularization,
+                           return_weights=return_weights)
+
 
 class XmrisFittingMixin:
     def fit_amares(self, prior_knowledge_file, dim: str = "time", mhz: float = None, sw: float = None,

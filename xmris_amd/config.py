@@ -70,6 +70,10 @@ class _Attrs(_Vocabulary):
     sense_dims = XmrisTerm("sense_dims", "Names of the undersampled dimensions the SENSE unfolding restored to the full field of view.")
     sense_accel = XmrisTerm("sense_accel", "Acceleration along each unfolded dimension.")
     sense_regularization = XmrisTerm("sense_regularization", "Tikhonov weight of the SENSE unfolding, relative to the mean diagonal of S^H Psi^-1 S.")
+    grappa_dims = XmrisTerm("grappa_dims", "Names of the undersampled k-space dimensions that GRAPPA filled to the full grid.")
+    grappa_accel = XmrisTerm("grappa_accel", "Acceleration along each filled dimension.")
+    grappa_kernel = XmrisTerm("grappa_kernel", "Acquired neighbour lines per filled dimension that one GRAPPA weight set combines.")
+    grappa_regularization = XmrisTerm("grappa_regularization", "Tikhonov weight of the GRAPPA calibration, relative to the mean diagonal of the source Gram matrix.")
     grid_dims = XmrisTerm("grid_dims", "Names of the dimensions that gridding put in place of the sample dimension.")
     grid_matrix = XmrisTerm("grid_matrix", "Target matrix along each gridded dimension.")
     grid_oversampled = XmrisTerm("grid_oversampled", "Points of the oversampled Cartesian grid along each gridded dimension.")

@@ -15,7 +15,7 @@
 #include <mutex>
 #include <tuple>
 
-#define XM_VERSION_NUM 400  // 0.4.0 (round 4: xm_search_*, xm_hostsearch_*, xm_stream_*, xm_zf_apod, xm_atomic_*, xm_last_kernel_string)
+#define XM_VERSION_NUM 500  // 0.5.0 (xm_grappa_fill; 0.4.0: xm_search_*, xm_hostsearch_*, xm_stream_*, xm_zf_apod, xm_atomic_*, xm_last_kernel_string)
 
 static thread_local std::string g_err;
 static thread_local std::string g_last_kernel;

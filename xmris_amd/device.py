@@ -695,6 +695,93 @@ def unfold_sense(x, sens, coil_axis: int, spatial_axes, time_axis: int, accel, l
     return SenseUnfold(y=y if y.is_contiguous() else y.contiguous(), g=g, status=status)
 
 
+GRAPPA_MAX_COILS = 64
+GRAPPA_MAX_ACCEL = 16
+GRAPPA_MAX_SOURCES = 64  # S = the product of the kernel sizes
+GRAPPA_MAX_TERMS = 1024  # C S
+
+
+def grappa_weights(weights, device):
+    """GRAPPA weights (host values or a tensor) as a contiguous complex128 tensor on `device`, as xm_grappa_fill reads them."""
+    torch = _torch()
+    if isinstance(weights, torch.Tensor):
+        return weights.to(device=device, dtype=torch.complex128).contiguous()
+    return torch.from_numpy(np.array(weights, dtype=np.complex128, order="C")).to(device)
+
+
+def grappa_fill(x, weights, coil_axis: int, spatial_axes, time_axis: int, accel, kernel):
+    """GRAPPA fill of the kept k-space lines in the complex64 / complex128 device tensor `x` in one launch
+    (xm_grappa_fill).  `spatial_axes`: 1 ... 3 undersampled axes, `accel` and `kernel`: the
+    acceleration and the number of neighbour lines along each; every axis but these, `coil_axis` and `time_axis` is
+    batch.  `weights`: [R - 1, C, S, C] complex (host values, uploaded at every call, or a device tensor, used where it lies when
+    it is contiguous complex128: ``grappa_weights``), None at R = 1.
+    Returns the tensor with every spatial axis grown to accel x its size, in the input's dtype and axis order but time
+    last.  With time last the coil and spatial axes are addressed where they lie; a tensor whose time axis is not
+    contiguous, or whose batch axes do not fold into one stride, costs one contiguous copy."""
+    torch = _torch()
+    _require_device(x)
+    nd = x.dim()
+    coil_axis, time_axis = coil_axis % nd, time_axis % nd
+    axes = [int(a) % nd for a in spatial_axes]
+    acc, ker = [int(r) for r in accel], [int(b) for b in kernel]
+    if not 1 <= len(axes) <= 3 or len(acc) != len(axes) or len(ker) != len(axes):
+        raise ValueError(f"spatial_axes: needs 1 ... 3 axes and one accel and one kernel size per axis, got {len(axes)}, "
+                         f"{len(acc)} and {len(ker)}")
+    if len({coil_axis, time_axis, *axes}) != len(axes) + 2:
+        raise ValueError("coil_axis, time_axis and spatial_axes must all differ")
+    rtot, stot = int(np.prod(acc)), int(np.prod(ker))
+    if any(r < 1 for r in acc) or rtot > GRAPPA_MAX_ACCEL:
+        raise ValueError(f"accel: every entry must be >= 1 and their product at most {GRAPPA_MAX_ACCEL}, got {acc}")
+    c, nt = int(x.shape[coil_axis]), int(x.shape[time_axis])
+    small = [int(x.shape[a]) for a in axes]
+    full = [r * n for r, n in zip(acc, small)]
+    if not 1 <= c <= GRAPPA_MAX_COILS or nt < 1 or min(small) < 1:
+        raise ValueError(f"needs 1 ... {GRAPPA_MAX_COILS} coils and no empty axis, got shape {tuple(x.shape)}")
+    if any(b < 1 for b in ker) or stot > GRAPPA_MAX_SOURCES or c * stot > GRAPPA_MAX_TERMS:
+        raise ValueError(f"kernel: every entry must be >= 1, their product at most {GRAPPA_MAX_SOURCES} and coils x product "
+                         f"at most {GRAPPA_MAX_TERMS}, got {ker} at {c} coils")
+    dev_ = x.device
+    w = None
+    if rtot > 1:
+        if weights is None:
+            raise ValueError("weights: needed when the product of accel exceeds 1")
+        w = grappa_weights(weights, dev_)
+        if tuple(w.shape) != (rtot - 1, c, stot, c):
+            raise ValueError(f"weights must be {[rtot - 1, c, stot, c]} (types, coils, sources, coils), got {list(w.shape)}")
+    batch = [a for a in range(nd) if a not in (coil_axis, time_axis, *axes)]
+
+    def folds(v):  # the batch axes in front of v fold into one stride
+        return all(v.stride(i) == v.stride(i + 1) * v.shape[i + 1] for i in range(len(batch) - 1))
+
+    xv = x.permute(batch + [coil_axis] + axes + [time_axis])
+    if xv.numel() and (xv.stride(-1) != 1 and nt > 1 or not folds(xv)):
+        xv = xv.contiguous()
+    code = _dtype_code(xv)
+    # y: batch axes in front, then the coil and spatial axes in the input's own order, then time
+    kept = sorted([coil_axis] + axes)
+    bshape = [int(x.shape[a]) for a in batch]
+    size = {coil_axis: c, **{a: f for a, f in zip(axes, full)}}
+    yc = torch.empty(bshape + [size[a] for a in kept] + [nt], dtype=x.dtype, device=dev_)
+    nb = len(batch)
+    yv = yc.permute(list(range(nb)) + [nb + kept.index(a) for a in [coil_axis] + axes] + [nb + len(kept)])
+    pad = 3 - len(axes)
+    n_outer = int(np.prod(bshape, dtype=np.int64))
+    if n_outer > 0:
+        def strides(v):
+            return ([int(v.stride(nb - 1)) if nb else 0, int(v.stride(nb))] + [0] * pad
+                    + [int(v.stride(nb + 1 + i)) for i in range(len(axes))])
+
+        i32, i64 = ctypes.c_int32 * 3, ctypes.c_int64 * 5
+        _lib.call("xm_grappa_fill", xv.data_ptr(), yc.data_ptr(), w.data_ptr() if w is not None else None, n_outer, c,
+                  i32(*([1] * pad + small)), i32(*([1] * pad + acc)), i32(*([1] * pad + ker)), nt, i64(*strides(xv)),
+                  i64(*strides(yv)), code, _stream(x))
+    # back to the input's axis order (time last)
+    order = [a for a in range(nd) if a != time_axis]
+    have = batch + kept
+    y = yc.permute([have.index(a) for a in order] + [len(have)])
+    return y if y.is_contiguous() else y.contiguous()
+
+
 class AlignRows:
     """Raw outputs of ``align_rows``, the input's axes other than time in front and in the input's order: y like x
     (time last) or None, shift (Hz), phase (rad), quality fp64 and status int32 per transient (0 aligned, 1 window edge,
