@@ -466,6 +466,37 @@ int xm_grappa_fill(const void* a, void* y, const void* weights, int64_t n_outer,
 int xm_axis_sparse(const void* x, void* y, const int32_t* rowptr, const int32_t* col, const double* val, int64_t n_outer,
                    int64_t n, int64_t n_rows, int64_t n_inner, int dtype, void* stream);
 
+/* ---- CG-SENSE: the image-sized half of a conjugate-gradient step (this backend's own definition,
+ * the reference has none).  V = n_vox voxels, T = n_cols independent columns, C = n_coils; all arrays C-contiguous in
+ * device memory: x, r, p, q [V, T] complex128; s [C, V] complex128; u [C, V, T] of `dtype` (XM_C64 / XM_C128), the coil
+ * images that enter or leave a NUFFT chain.  A sum over voxels is kept as partials [NB, T] fp64, NB = ceil(V /
+ * XM_CGS_VOXELS): partial [b, t] is the sum over the voxels of block b in ascending v, and a total is the sum of the NB
+ * partials of a column in ascending b.  Every product-sum is a fused multiply-add in fp64; u rounds once to `dtype`.
+ *   xm_cgs_expand: for a column with status[t] == 0, p <- r + (rho_new / rho_old) p (the totals of the two partial
+ *     arrays; `first` != 0: p <- r and the partials are not read, though the pointers must be valid); then for every column u[c, v, t] = s[c, v] p[v, t].
+ *   xm_cgs_reduce: q[v, t] = sum_c conj(s[c, v]) u[c, v, t] (ascending c) + lambda p[v, t], part[b, t] = sum_v Re(conj(p) q).
+ *     `initial` != 0: no lambda term, p is not read (may be NULL) and part[b, t] = sum_v |q|^2: q is then b = E^H D y.
+ *   xm_cgs_step: for a column with status_in[t] == 0, in this order: the total of rho0 not finite -> status 3 and
+ *     x[:, t] = NaN; the total of rho <= max(tol, 1e-14)^2 x that of rho0 -> status 1; `final_test` != 0 -> status stays
+ *     0; the total of delta not > 0 or not finite -> status 2; otherwise alpha = rho / delta, x += alpha p, r -= alpha q,
+ *     rho_out[b, t] = sum_v |r|^2, n_iter[t] = iteration.  status_out[t] is written for every column; residual[t] =
+ *     sqrt(rho / rho0) (0 for rho0 = 0, NaN with status 3) for a column that leaves status 0 in this call, and in a final test for one that
+ *     stays 0.  A column with status_in[t] != 0 is not touched.  With `final_test`, delta is not read (may be NULL).
+ * No call reads a per-column value that the same call writes (the caller alternates two buffers for the partials of rho
+ * and for status), there are no atomics, and a column depends on its own values only: results are bitwise independent of
+ * the other columns of the call.  All sizes in 1 ... 2^31 - 1, at most 2^50 elements in u, non-NULL pointers aligned to
+ * their element size, no output equal to an input or to another output, a known dtype, a finite lambda and tol >= 0 and
+ * iteration >= 0: otherwise XM_ERR_INVALID_ARG before any HIP call. */
+#define XM_CGS_VOXELS 16
+int xm_cgs_expand(const void* r, void* p, const void* s, void* u, const double* rho_new, const double* rho_old,
+                  const int32_t* status, int64_t n_coils, int64_t n_vox, int64_t n_cols, int first, int dtype,
+                  void* stream);
+int xm_cgs_reduce(const void* u, const void* s, const void* p, void* q, double* part, int64_t n_coils, int64_t n_vox,
+                  int64_t n_cols, double lambda, int initial, int dtype, void* stream);
+int xm_cgs_step(void* x, void* r, const void* p, const void* q, const double* rho, const double* rho0,
+                const double* delta, double* rho_out, const int32_t* status_in, int32_t* status_out, int32_t* n_iter,
+                double* residual, int64_t n_vox, int64_t n_cols, double tol, int iteration, int final_test, void* stream);
+
 /* ---- Per-row time shift of FIDs (this backend's own definition, the reference has none).
  * `in`: n_rows rows of n points, `in_row_stride` elements apart; `out`: n_rows contiguous rows of n points.  Row r is
  * delayed by phi = frac[(r / delay_div) % n_delay] dwells (`frac`: n_delay fp64 in device memory):

@@ -43,6 +43,7 @@ XM_DENOISE_STOP_GRAM = 0x200
 XM_DENOISE_STOP_EIG = 0x400
 
 XM_SENSE_WORKSPACE_BYTES = 256
+XM_CGS_VOXELS = 16
 
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
@@ -97,6 +98,9 @@ SIGNATURES = {
     "xm_sense_unfold": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _i, _p, _p, ctypes.c_double, _i, _p, _p]),
     "xm_grappa_fill": (_i, [_p, _p, _p, _l, _i, _p, _p, _p, _i, _p, _p, _i, _p]),
     "xm_axis_sparse": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _p]),
+    "xm_cgs_expand": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p]),
+    "xm_cgs_reduce": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, ctypes.c_double, _i, _i, _p]),
+    "xm_cgs_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, ctypes.c_double, _i, _i, _p]),
     "xm_shift_time_fused": (_i, [_i, _i]),
     "xm_shift_time": (_i, [_p, _l, _p, _l, _i, _i, _p, _l, _l, _i, _p]),
     "xm_kinetics_fit": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, ctypes.c_double, ctypes.c_double, _p, _p,

@@ -176,6 +176,19 @@ class XmrisMrsiMixin:
         return nufft_forward(self._obj, trajectory, matrix=matrix, oversampling=oversampling, width=width, dim=dim,
                              out_dim=out_dim, readout_time=readout_time)
 
+    def recon_cg_sense(self, trajectory, sensitivities, matrix=None, iterations: int = 20, tol: float = 1e-6,
+                       regularization: float = 0.0, density=None, noise_cov=None, oversampling: float = 2.0,
+                       width: int = 4, dim: str = DIMS.sample, coil_dim: str = DIMS.coil, out_dim=None, fov=1.0,
+                       readout_time=None, chunk=None, return_info: bool = False):
+        """Iterative SENSE of multi-coil, undersampled, non-Cartesian samples: conjugate gradients around the two NUFFT
+        chains, every column on its own (an addition of this backend)."""
+        from .processing.cgsense import recon_cg_sense
+
+        return recon_cg_sense(self._obj, trajectory, sensitivities, matrix=matrix, iterations=iterations, tol=tol,
+                              regularization=regularization, density=density, noise_cov=noise_cov,
+                              oversampling=oversampling, width=width, dim=dim, coil_dim=coil_dim, out_dim=out_dim, fov=fov,
+                              readout_time=readout_time, chunk=chunk, return_info=return_info)
+
     def shift_time(self, delay, dim: str = DIMS.time, pad_to=None, dwell=None):
         """Each row along `dim` evaluated `delay` earlier, one fused launch (an addition of this backend; DESIGN.md
         section 18)."""

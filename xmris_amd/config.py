@@ -80,6 +80,9 @@ class _Attrs(_Vocabulary):
     grid_width = XmrisTerm("grid_width", "Width of the Kaiser-Bessel gridding kernel.", "grid cells")
     grid_beta = XmrisTerm("grid_beta", "Shape parameter of the Kaiser-Bessel gridding kernel along each gridded dimension.")
     grid_density = XmrisTerm("grid_density", "Density compensation of the gridding: 'none', 'pipe' or 'custom'.")
+    cgsense_iterations = XmrisTerm("cgsense_iterations", "Iteration cap of the CG-SENSE reconstruction.")
+    cgsense_tol = XmrisTerm("cgsense_tol", "Relative residual at which a column of the CG-SENSE reconstruction stops.")
+    cgsense_regularization = XmrisTerm("cgsense_regularization", "Tikhonov weight of the CG-SENSE reconstruction, relative to the mean diagonal of the normal matrix.")
     time_shift_pad_to = XmrisTerm("time_shift_pad_to", "Transform length of the last time shift along the FID axis.")
     readout_time_corrected = XmrisTerm("readout_time_corrected", "Whether the acquisition delays of the readout's samples have been removed.")
     kinetics_model = XmrisTerm("kinetics_model", "Rate model that fit_kinetics fitted along the repetitions.")

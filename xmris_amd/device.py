@@ -1125,6 +1125,135 @@ def axis_sparse(x, axis: int, table: SparseTable):
     return out
 
 
+CGS_MAX_COILS = 64
+CGS_VOXELS = _lib.XM_CGS_VOXELS
+
+
+def cgs_blocks(n_vox: int) -> int:
+    """Voxel blocks, i.e. partials per column, of the CG-SENSE kernels."""
+    return (int(n_vox) + CGS_VOXELS - 1) // CGS_VOXELS
+
+
+def _cgs_c128(x, shape, what: str):
+    torch = _torch()
+    _require_device(x)
+    if x.dtype != torch.complex128 or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous complex128 tensor of shape {tuple(shape)}, got {tuple(x.shape)} of {x.dtype}")
+    return x
+
+
+def _cgs_plain(x, dtype, shape, what: str):
+    _require_device(x)
+    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {tuple(x.shape)} of {x.dtype}")
+    return x
+
+
+def cgs_expand(r, p, s, rho_new, rho_old, status, first: bool, dtype, out=None):
+    """One launch of k_cgs_expand (xm_cgs_expand): in place ``p <- r + (rho_new / rho_old) p`` for the
+    columns whose `status` is 0 (``p <- r`` when `first`), then returns ``u[c, v, t] = s[c, v] p[v, t]`` rounded to `dtype`
+    (torch.complex64 / complex128), [C, V, T].  r, p: [V, T] complex128; s: [C, V] complex128; rho_new, rho_old: the
+    [NB, T] fp64 partials of this and the previous step's rho (read only when not `first`); status: [T] int32."""
+    torch = _torch()
+    c, v = (int(n) for n in s.shape)
+    t = int(r.shape[1])
+    _cgs_c128(r, (v, t), "r"), _cgs_c128(p, (v, t), "p"), _cgs_c128(s, (c, v), "s")
+    nb = cgs_blocks(v)
+    _cgs_plain(rho_new, torch.float64, (nb, t), "rho_new"), _cgs_plain(rho_old, torch.float64, (nb, t), "rho_old")
+    _cgs_plain(status, torch.int32, (t,), "status")
+    u = torch.empty((c, v, t), dtype=dtype, device=r.device) if out is None else _cgs_plain(out, dtype, (c, v, t), "out")
+    _lib.call("xm_cgs_expand", r.data_ptr(), p.data_ptr(), s.data_ptr(), u.data_ptr(), rho_new.data_ptr(), rho_old.data_ptr(),
+              status.data_ptr(), c, v, t, int(bool(first)), _dtype_code(u), _stream(r))
+    return u
+
+
+def cgs_reduce(u, s, p, q, part, lam: float = 0.0, initial: bool = False):
+    """One launch of k_cgs_reduce (xm_cgs_reduce): ``q[v, t] = sum_c conj(s[c, v]) u[c, v, t] + lam p[v, t]`` and the
+    [NB, T] partials of ``Re<p, q>`` into `part`; `initial`: no `lam` term, `p` is not read (may be None) and the partials
+    are those of ``|q|^2``.  u: [C, V, T] complex64 / complex128; s, p, q as in `cgs_expand`."""
+    torch = _torch()
+    _require_device(u)
+    c, v, t = (int(n) for n in u.shape)
+    if not u.is_contiguous():
+        raise ValueError("u must be contiguous")
+    _cgs_c128(s, (c, v), "s"), _cgs_c128(q, (v, t), "q")
+    if not initial:
+        _cgs_c128(p, (v, t), "p")
+    _cgs_plain(part, torch.float64, (cgs_blocks(v), t), "part")
+    _lib.call("xm_cgs_reduce", u.data_ptr(), s.data_ptr(), None if initial else p.data_ptr(), q.data_ptr(), part.data_ptr(),
+              c, v, t, float(lam), int(bool(initial)), _dtype_code(u), _stream(u))
+    return q, part
+
+
+def cgs_step(x, r, p, q, rho, rho0, delta, rho_out, status_in, status_out, n_iter, residual, tol: float, iteration: int,
+             final: bool = False):
+    """One launch of k_cgs_step (xm_cgs_step): per column whose `status_in` is 0 the stopping rules and, where none holds,
+    ``alpha = rho / delta, x += alpha p, r -= alpha q``, the partials of ``|r|^2`` into `rho_out` and ``n_iter =
+    iteration``; `final`: the rules alone (`delta` may be None).  rho, rho0, delta, rho_out: [NB, T] fp64 partials;
+    status_in, status_out, n_iter: [T] int32; residual: [T] fp64."""
+    torch = _torch()
+    v, t = (int(n) for n in x.shape)
+    nb = cgs_blocks(v)
+    for a, name in ((x, "x"), (r, "r"), (p, "p"), (q, "q")):
+        _cgs_c128(a, (v, t), name)
+    for a, name in ((rho, "rho"), (rho0, "rho0"), (rho_out, "rho_out")) + (() if final else ((delta, "delta"),)):
+        _cgs_plain(a, torch.float64, (nb, t), name)
+    for a, name in ((status_in, "status_in"), (status_out, "status_out"), (n_iter, "n_iter")):
+        _cgs_plain(a, torch.int32, (t,), name)
+    _cgs_plain(residual, torch.float64, (t,), "residual")
+    _lib.call("xm_cgs_step", x.data_ptr(), r.data_ptr(), p.data_ptr(), q.data_ptr(), rho.data_ptr(), rho0.data_ptr(),
+              None if final else delta.data_ptr(), rho_out.data_ptr(), status_in.data_ptr(), status_out.data_ptr(),
+              n_iter.data_ptr(), residual.data_ptr(), v, t, float(tol), int(iteration), int(bool(final)), _stream(x))
+
+
+class CgSense:
+    """Raw outputs of ``cg_sense``: x [V, T] complex128; residual [T] fp64 (sqrt(rho / rho0) at the last test of the
+    column); iterations [T] int32; status [T] int32 (0 iteration cap, 1 converged, 2 breakdown: <p, A p> not positive,
+    3 a right-hand side that is not finite: x is NaN)."""
+
+    __slots__ = ("x", "residual", "iterations", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def cg_sense(y, s, adjoint, forward, lam: float, iterations: int, tol: float) -> CgSense:
+    """Conjugate gradients on ``(E^H D E + lam I) x = E^H D y`` from x = 0, every column on its own (DESIGN.md section
+    21).  y: [C, S, T] complex64 / complex128, contiguous; s: [C, V] complex128; `adjoint`: [C, S, T] -> the coil images
+    [C, V, T] (gridding with the density, transform, crop), `forward`: its transpose with unit density -- the two NUFFT
+    chains on raw tensors.  Queues a fixed sequence of launches, 3 of this module per iteration around the chains',
+    and reads nothing back: the caller synchronises when it looks at the result."""
+    torch = _torch()
+    _require_device(y)
+    c, v = (int(n) for n in s.shape)
+    t = int(y.shape[2])
+    dev_ = y.device
+    nb = cgs_blocks(v)
+    c128 = dict(dtype=torch.complex128, device=dev_)
+    x = torch.zeros((v, t), **c128)
+    r, p, q = (torch.empty((v, t), **c128) for _ in range(3))
+    rho0, delta = (torch.empty((nb, t), dtype=torch.float64, device=dev_) for _ in range(2))
+    rho = torch.empty((2, nb, t), dtype=torch.float64, device=dev_)
+    status = torch.zeros((2, t), dtype=torch.int32, device=dev_)
+    n_iter = torch.zeros(t, dtype=torch.int32, device=dev_)
+    residual = torch.zeros(t, dtype=torch.float64, device=dev_)
+
+    cgs_reduce(adjoint(y).reshape(c, v, t), s, None, r, rho0, initial=True)
+    for k in range(iterations):
+        now = rho0 if k == 0 else rho[k % 2]
+        before = rho0 if k <= 1 else rho[(k - 1) % 2]
+        u = cgs_expand(r, p, s, now, before, status[k % 2], k == 0, y.dtype)
+        u = adjoint(forward(u)).reshape(c, v, t)
+        cgs_reduce(u, s, p, q, delta, lam)
+        cgs_step(x, r, p, q, now, rho0, delta, rho[(k + 1) % 2], status[k % 2], status[(k + 1) % 2], n_iter, residual, tol,
+                 k + 1)
+    n = iterations
+    cgs_step(x, r, p, q, rho0 if n == 0 else rho[n % 2], rho0, None, rho[(n + 1) % 2], status[n % 2], status[(n + 1) % 2],
+             n_iter, residual, tol, n, final=True)
+    return CgSense(x=x, residual=residual, iterations=n_iter, status=status[(n + 1) % 2])
+
+
 def shift_time_fused(L: int, complex128: bool = False) -> bool:
     """True when `shift_time` runs transform length `L` as one launch of k_shift_time (`xm_shift_time_fused`)."""
     return bool(_lib.load().xm_shift_time_fused(int(L), _lib.XM_C128 if complex128 else _lib.XM_C64))

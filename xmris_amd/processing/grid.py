@@ -279,6 +279,41 @@ def _narrow(x, axis: int, start: int, length: int):
     return y.contiguous() if hasattr(y, "contiguous") else np.ascontiguousarray(y)
 
 
+def _image_tables(t: GridTable, sign: float):
+    """Per dim what the transform between the oversampled grid and the voxels needs: the [m, G] table F (sign = +1) or
+    F^H (sign = -1) where G fits ``axis_dft``, else the complex vector c of the staged transform."""
+    return [_image_table(m, G, c, sign) if G <= dev.AXIS_DFT_MAX else c + 0j
+            for m, G, c in zip(t.matrix, t.oversampled, t.deapodization)]
+
+
+def _to_voxels(y, axis: int, t: GridTable, tables):
+    """The gridded samples `y` (flat cell axis at `axis`) -> voxels: per dim one ``axis_dft`` launch, or for G > 64 the
+    centred transform of ``to_image`` on G, the crop and the product with c.  `tables`: ``_image_tables(t, 1.0)``, host
+    values or already on the device."""
+    shape = tuple(y.shape)
+    y = y.reshape(shape[:axis] + tuple(t.oversampled) + shape[axis + 1:])
+    for a, (m, G) in enumerate(zip(t.matrix, t.oversampled)):
+        if G <= dev.AXIS_DFT_MAX:
+            y = dev.axis_dft(y, axis + a, tables[a])
+        else:
+            y = dev.fft(y, axis + a, inverse=True, ortho=True, shift_in=True, shift_out=True)
+            y = dev.phase_apply(_narrow(y, axis + a, G // 2 - m // 2, m), axis + a, tables[a])
+    return y
+
+
+def _to_samples(x, axis: int, t: GridTable, tables):
+    """Voxels (the image dims from `axis` on) -> samples: the transposed chain of `_to_voxels` and degridding.
+    `tables`: ``_image_tables(t, -1.0)``."""
+    for a, (m, G) in enumerate(zip(t.matrix, t.oversampled)):
+        if G <= dev.AXIS_DFT_MAX:
+            x = dev.axis_dft(x, axis + a, tables[a])
+        else:
+            x = dev.phase_apply(x, axis + a, tables[a])
+            x = dev.zero_fill(x, axis + a, G, pad_left=G // 2 - m // 2)
+            x = dev.fft(x, axis + a, inverse=False, ortho=True, shift_in=True, shift_out=True)
+    return _apply_degrid(x, axis, t)
+
+
 def nufft_adjoint(da, trajectory, matrix, oversampling: float = 2.0, width: int = 4, density=None,
                   dim: str = DIMS.sample, out_dim=None, fov=1.0, iterations: int = PIPE_ITERATIONS, readout_time=None):
     """Non-Cartesian samples -> voxels: ``grid_kspace``, then per dim the centred inverse transform, the crop to
@@ -289,14 +324,7 @@ def nufft_adjoint(da, trajectory, matrix, oversampling: float = 2.0, width: int 
     da = _readout(da, readout_time, dim, False)
     src, y, axis, names, t, f = _grid(da, trajectory, matrix, oversampling, width, density, iterations, dim, out_dim, fov,
                                       "nufft_adjoint")
-    shape = tuple(y.shape)
-    y = y.reshape(shape[:axis] + tuple(t.oversampled) + shape[axis + 1:])
-    for a, (m, G, c) in enumerate(zip(t.matrix, t.oversampled, t.deapodization)):
-        if G <= dev.AXIS_DFT_MAX:
-            y = dev.axis_dft(y, axis + a, _image_table(m, G, c, 1.0))
-        else:  # the centred transform of to_image on G, the crop and c
-            y = dev.fft(y, axis + a, inverse=True, ortho=True, shift_in=True, shift_out=True)
-            y = dev.phase_apply(_narrow(y, axis + a, G // 2 - m // 2, m), axis + a, c + 0j)
+    y = _to_voxels(y, axis, t, _image_tables(t, 1.0))
     dims, coords = _expand(src, dim, names, lambda a: (np.arange(t.matrix[a]) - t.matrix[a] // 2) * f[a] / t.matrix[a])
     return like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, _label(density)), src.name), da)
 
@@ -384,14 +412,7 @@ def nufft_forward(da, trajectory, matrix=None, oversampling: float = 2.0, width:
     src, x, axis, names, t = _degrid(da, k, matrix, oversampling, width, names, out_dim, X_DIMS, "nufft_forward", True)
     if hasattr(x, "contiguous"):
         x = x.contiguous()
-    for a, (m, G, c) in enumerate(zip(t.matrix, t.oversampled, t.deapodization)):
-        if G <= dev.AXIS_DFT_MAX:
-            x = dev.axis_dft(x, axis + a, _image_table(m, G, c, -1.0))
-        else:
-            x = dev.phase_apply(x, axis + a, c + 0j)
-            x = dev.zero_fill(x, axis + a, G, pad_left=G // 2 - m // 2)
-            x = dev.fft(x, axis + a, inverse=False, ortho=True, shift_in=True, shift_out=True)
-    y = _apply_degrid(x, axis, t)
+    y = _to_samples(x, axis, t, _image_tables(t, -1.0))
     dims, coords = _collapse(src, names, out_dim, t.grid.n)
     return _readout(like_input(LabeledArray(y, dims, coords, _attrs(src, names, t, "none"), src.name), da), readout_time,
                     out_dim, True)
