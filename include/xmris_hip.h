@@ -497,6 +497,23 @@ int xm_cgs_step(void* x, void* r, const void* p, const void* q, const double* rh
                 const double* delta, double* rho_out, const int32_t* status_in, int32_t* status_out, int32_t* n_iter,
                 double* residual, int64_t n_vox, int64_t n_cols, double tol, int iteration, int final_test, void* stream);
 
+/* ---- ESPIRiT: per-voxel eigen-decomposition of a coil x coil Hermitian matrix (this backend's own
+ * definition, the reference has none).  h: [n_vox, E] complex128, E = C (C + 1) / 2, C = n_coils: per voxel the upper
+ * triangle (i <= j) of its matrix in row-major order; the lower triangle is the conjugate and the imaginary part of the
+ * diagonal is ignored.  One launch of k_espirit_eig, one 256-thread workgroup per voxel, parallel cyclic Jacobi in fp64.
+ * For m < n_maps the m-th largest eigenvalue (a tie goes to the lower column of the Jacobi result) goes to values[m, v]
+ * and its eigenvector to maps[m, :, v] (maps: [n_maps, C, n_vox] complex128; values: [n_maps, n_vox] fp64), of unit norm
+ * and multiplied by the phase that makes component `phase_ref` real and >= 0 (left as it is when that component is
+ * exactly 0).  A map whose eigenvalue is < crop is written as exact zeros.  status[v] (int32): 0 ok; 1 the sweep cap was
+ * reached, the outputs are those of the last sweep; 2 a non-finite entry (or finite ones whose norm overflows): maps 0,
+ * values NaN.  A zero matrix has status 0 and eigenvalue 0.  No atomics, no voxel reads another's data and every sum has
+ * a fixed order: a voxel's outputs are bitwise independent of n_vox and of its place in the batch.  n_coils in 1 ... 64,
+ * n_maps in 1 ... min(2, n_coils), n_vox in 1 ... 2^31 - 1, phase_ref in 0 ... n_coils - 1, a finite crop, non-NULL
+ * pointers aligned to their element size, no output equal to the input or to another output: otherwise
+ * XM_ERR_INVALID_ARG before any HIP call. */
+int xm_espirit_eig(const void* h, void* maps, double* values, int32_t* status, int64_t n_vox, int n_coils, int n_maps,
+                   int phase_ref, double crop, void* stream);
+
 /* ---- Per-row time shift of FIDs (this backend's own definition, the reference has none).
  * `in`: n_rows rows of n points, `in_row_stride` elements apart; `out`: n_rows contiguous rows of n points.  Row r is
  * delayed by phi = frac[(r / delay_div) % n_delay] dwells (`frac`: n_delay fp64 in device memory):

@@ -101,6 +101,7 @@ SIGNATURES = {
     "xm_cgs_expand": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p]),
     "xm_cgs_reduce": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, ctypes.c_double, _i, _i, _p]),
     "xm_cgs_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, ctypes.c_double, _i, _i, _p]),
+    "xm_espirit_eig": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, ctypes.c_double, _p]),
     "xm_shift_time_fused": (_i, [_i, _i]),
     "xm_shift_time": (_i, [_p, _l, _p, _l, _i, _i, _p, _l, _l, _i, _p]),
     "xm_kinetics_fit": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, ctypes.c_double, ctypes.c_double, _p, _p,

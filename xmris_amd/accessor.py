@@ -189,6 +189,17 @@ class XmrisMrsiMixin:
                               oversampling=oversampling, width=width, dim=dim, coil_dim=coil_dim, out_dim=out_dim, fov=fov,
                               readout_time=readout_time, chunk=chunk, return_info=return_info)
 
+    def espirit_maps(self, matrix, kernel=None, dims=(DIMS.kx, DIMS.ky), coil_dim: str = DIMS.coil,
+                     time_dim: str = DIMS.time, acs_points: int = 8, threshold: float = 0.02, crop: float = 0.8,
+                     n_maps: int = 1, noise_cov=None, phase_ref: int = 0, return_eigenvalues: bool = False):
+        """ESPIRiT coil sensitivities from this auto-calibration block of k-space, for ``unfold_sense`` and
+        ``recon_cg_sense`` (an addition of this backend)."""
+        from .processing.espirit import espirit_maps
+
+        return espirit_maps(self._obj, matrix, kernel=kernel, dims=dims, coil_dim=coil_dim, time_dim=time_dim,
+                            acs_points=acs_points, threshold=threshold, crop=crop, n_maps=n_maps, noise_cov=noise_cov,
+                            phase_ref=phase_ref, return_eigenvalues=return_eigenvalues)
+
     def shift_time(self, delay, dim: str = DIMS.time, pad_to=None, dwell=None):
         """Each row along `dim` evaluated `delay` earlier, one fused launch (an addition of this backend; DESIGN.md
         section 18)."""

@@ -1254,6 +1254,48 @@ def cg_sense(y, s, adjoint, forward, lam: float, iterations: int, tol: float) ->
     return CgSense(x=x, residual=residual, iterations=n_iter, status=status[(n + 1) % 2])
 
 
+class EspiritEig:
+    """Raw outputs of ``espirit_eig``: maps [M, C, V] complex128, values [M, V] fp64 (descending over M), status [V]
+    int32 (0 ok, 1 Jacobi sweep cap, 2 non-finite entry: maps 0, values NaN)."""
+
+    __slots__ = ("maps", "values", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+ESPIRIT_MAX_COILS = 64
+
+
+def espirit_entries(c: int) -> int:
+    """Entries of the upper triangle of a c x c matrix, the trailing axis of ``espirit_eig``'s input."""
+    return int(c) * (int(c) + 1) // 2
+
+
+def espirit_eig(h, n_coils: int, n_maps: int = 1, phase_ref: int = 0, crop: float = 0.8) -> EspiritEig:
+    """The `n_maps` (1 or 2) largest eigenpairs of one Hermitian matrix per voxel in one launch (xm_espirit_eig,
+    DESIGN.md section 22).  h: [V, E] complex128 device tensor, per voxel the upper triangle (i <= j, row-major) of its
+    `n_coils` x `n_coils` matrix, E = n_coils (n_coils + 1) / 2.  Each eigenvector has unit norm and its component
+    `phase_ref` real and >= 0; a map whose eigenvalue is below `crop` is exact zeros."""
+    torch = _torch()
+    _require_device(h)
+    c, m = int(n_coils), int(n_maps)
+    if not 1 <= c <= ESPIRIT_MAX_COILS:
+        raise ValueError(f"n_coils must be in 1 ... {ESPIRIT_MAX_COILS}, got {n_coils!r}")
+    if h.dtype != torch.complex128 or h.dim() != 2 or h.shape[1] != espirit_entries(c) or h.shape[0] < 1:
+        raise ValueError(f"h must be a complex128 tensor [V >= 1, {espirit_entries(c)}] for {c} coils, got "
+                         f"{tuple(h.shape)} of {h.dtype}")
+    hc = h if h.is_contiguous() else h.contiguous()
+    v = int(hc.shape[0])
+    maps = torch.empty((m, c, v), dtype=torch.complex128, device=h.device)
+    values = torch.empty((m, v), dtype=torch.float64, device=h.device)
+    status = torch.empty((v,), dtype=torch.int32, device=h.device)
+    _lib.call("xm_espirit_eig", hc.data_ptr(), maps.data_ptr(), values.data_ptr(), status.data_ptr(), v, c, m,
+              int(phase_ref), float(crop), _stream(h))
+    return EspiritEig(maps=maps, values=values, status=status)
+
+
 def shift_time_fused(L: int, complex128: bool = False) -> bool:
     """True when `shift_time` runs transform length `L` as one launch of k_shift_time (`xm_shift_time_fused`)."""
     return bool(_lib.load().xm_shift_time_fused(int(L), _lib.XM_C128 if complex128 else _lib.XM_C64))

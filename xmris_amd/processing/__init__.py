@@ -3,6 +3,7 @@ from .align import align_averages
 from .baseline import baseline_als
 from .coils import combine_coils
 from .denoise import denoise_mppca
+from .espirit import espirit_maps
 from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .grappa import GrappaWeights, grappa_calibrate, grappa_fill
 from .cgsense import recon_cg_sense
@@ -17,7 +18,7 @@ from .water import remove_water
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense",
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense",
-           "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill"]
+           "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled
