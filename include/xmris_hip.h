@@ -560,6 +560,43 @@ int xm_kinetics_fit(const double* substrate, const double* products, const doubl
                     double ftol, double xtol, double* params, double* param_sd, double* rss, int32_t* status,
                     int32_t* iters, double* fit, double* auc_ratio, void* stream);
 
+/* ---- Multi-echo chemical-species separation (this backend's own definition, the reference has
+ * none).  A row (a k-space sample or a voxel) has E = n_echoes echoes at t_e = TE_e + tau_r and columns (coils) that
+ * share its readout delay tau_r [s] and field offset psi_r [Hz]; M = n_species species of frequency f_m [Hz] and decay
+ * R_m [1/s]:  y[e, c] = sum_m rho[m, c] e^{(2 pi i f_m - R_m) t_e} e^{2 pi i psi_r t_e}.  One launch of k_species writes
+ *   rho[m, c] = e^{-(2 pi i f_m - R_m) tau_r} sum_e P0[m, e] e^{-2 pi i psi_r t_e} y[e, c],   P0 = pinv(A0),
+ *   A0[e, m] = e^{(2 pi i f_m - R_m) TE_e}, all arithmetic fp64, the result rounded once to `dtype`.
+ * The data are addressed where they lie.  `dims` (HOST, 4): sizes of the outer and inner row level and of the outer
+ * and inner column level (>= 1; a level that is not needed has size 1).  `x_strides`, `y_strides` (HOST, 5): strides
+ * in elements of these four levels and of the echo (in y: the species) level.  `tau`, `psi`: fp64 device arrays read at
+ * r0 s0 + r1 s1 with the strides given (0 repeats a value), or NULL for 0.  Lanes run along the inner row level.
+ * `tables` (device, fp64): TE[E], f[M], R[M], P0[M][E] as (re, im); with `fit` also Pi[e][e] (E values) and Pi[e'][e] as
+ * (re, im) for the pairs e < e' in ascending order (e, e'), Pi = Q Q^H the projector onto range(A0).
+ * fit != 0: psi is not read; per row psi* maximises G(psi) = sum_e W[e, e] + 2 sum_{e<e'} Re(W[e, e'] e^{2 pi i psi
+ * (TE_e' - TE_e)}), W[e, e'] = Pi[e', e] sum_c y[e, c] conj(y[e', c]): the arg-max on the grid g delta, |g| <= G =
+ * floor(max_field / delta), delta = 1 / (4 span), span = max TE - min TE (HOST argument), a tie to the smaller |g|,
+ * then to the negative g; then the zero of G' in [(g* - 1) delta, (g* + 1) delta] within +-max_field by the
+ * safeguarded Newton iteration of xm_align_rows (step <= 2^-40 delta, or 40 steps).
+ * Outputs per row (nr0, nr1 contiguous): field (psi* or the given psi), residual (fit only, max(0, 1 - G(psi*) /
+ * sum |y|^2); may be NULL otherwise and is then not written), status: 0 done; 1 |g*| = G > 0 and G still rises at that
+ * end of the window (psi* is the end, unrefined); 2 a non-finite sample, tau or psi (species 0, field and residual
+ * NaN); 3 an all-zero row (psi* = 0 with fit, species 0, residual 0); 4 the step cap.  A row's outputs depend on its own
+ * samples and the scalar arguments only, bit for bit.
+ * `dtype`: XM_C64 / XM_C128; XM_SPECIES_SKIP_* on top of it leave a stage out (timing only).
+ * XM_ERR_INVALID_ARG before any HIP call, nothing written: E outside 2 ... 32 (2 ... 16 with fit), M outside 1 ... 8,
+ * M > E (M >= E with fit), a size < 1 (the row sizes may be 0: nothing is launched), more than 2^31 - 1 tiles of 64
+ * rows, a null pointer (but tau, psi, and residual without fit), with fit a max_field or span that is not finite and
+ * positive or a grid 2 G + 1 > 1025, an unknown dtype. */
+#define XM_SPECIES_SKIP_GRAM 0x100
+#define XM_SPECIES_SKIP_COARSE 0x200
+#define XM_SPECIES_SKIP_REFINE 0x400
+#define XM_SPECIES_SKIP_APPLY 0x800
+int xm_species_separate(const void* x, void* y, const int64_t* dims, const int64_t* x_strides, const int64_t* y_strides,
+                        int n_echoes, int n_species, const double* tables, const double* tau, int64_t tau_s0,
+                        int64_t tau_s1, const double* psi, int64_t psi_s0, int64_t psi_s1, double* field,
+                        double* residual, int32_t* status, int fit, double max_field, double span, int dtype,
+                        void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -207,6 +207,17 @@ class XmrisMrsiMixin:
 
         return shift_time(self._obj, delay, dim=dim, pad_to=pad_to, dwell=dwell)
 
+    def separate_species(self, frequencies, echo_times=None, dim: str = DIMS.echo, out_dim: str = DIMS.species, decay=None,
+                         readout_time=None, sample_dim: str = DIMS.sample, field_map=None, fit_field: bool = False,
+                         max_field=None, share=(DIMS.coil,), return_field: bool = False):
+        """Chemical-species amplitudes from a few echoes by least squares (an addition of this backend; DESIGN.md
+        section 23)."""
+        from .processing.species import separate_species
+
+        return separate_species(self._obj, frequencies, echo_times=echo_times, dim=dim, out_dim=out_dim, decay=decay,
+                                readout_time=readout_time, sample_dim=sample_dim, field_map=field_map,
+                                fit_field=fit_field, max_field=max_field, share=share, return_field=return_field)
+
     def correct_readout_time(self, offsets, dim: str = DIMS.time, sample_dim: str = DIMS.sample, pad_to=None, dwell=None,
                              inverse: bool = False):
         """Undo the acquisition delay of each sample of a non-Cartesian readout."""

@@ -92,6 +92,12 @@ class _Attrs(_Vocabulary):
     kinetics_rate_bounds = XmrisTerm("kinetics_rate_bounds", "Bounds of the fitted conversion rate.", "1/s")
     kinetics_decay_bounds = XmrisTerm("kinetics_decay_bounds", "Bounds of each product's effective decay rate (equal: fixed).", "1/s")
     kinetics_fit_initial = XmrisTerm("kinetics_fit_initial", "Whether the products' magnetisation before the first excitation was fitted.")
+    species_frequencies = XmrisTerm("species_frequencies", "Name and frequency of each chemical species that was separated from the echoes.", "Hz")
+    species_echo_times = XmrisTerm("species_echo_times", "Echo times the species were separated from.", "s")
+    species_decay = XmrisTerm("species_decay", "Decay rate of each species in the separation model.", "1/s")
+    species_nsa = XmrisTerm("species_nsa", "Effective number of signal averages of each species' estimate.")
+    species_field = XmrisTerm("species_field", "Field offset of the separation model: 'none', 'given' or 'fitted'.")
+    species_max_field = XmrisTerm("species_max_field", "Largest field offset the fit searched.", "Hz")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 
@@ -103,6 +109,7 @@ class _Dims(_Vocabulary):
     average = XmrisTerm("average", "Signal averages.")
     coil = XmrisTerm("coil", "Receive coils.")
     echo = XmrisTerm("echo", "Echoes.")
+    species = XmrisTerm("species", "Chemical species separated from the echoes.")
     sample = XmrisTerm("sample", "Samples of a non-Cartesian k-space trajectory.")
     kx = XmrisTerm("kx", "k-space axis x.")
     ky = XmrisTerm("ky", "k-space axis y.")

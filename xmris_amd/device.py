@@ -1357,6 +1357,173 @@ def shift_time(x, axis: int, frac, n_delay: int | None = None, delay_div: int = 
     return restore(y[:, :n].contiguous() if L > n else y)
 
 
+class SpeciesResult:
+    """Raw outputs of ``species_separate``: species like x with the echo axis replaced by the M species; per row (the
+    axes that are neither echo nor columns, in the input's order) field fp64 (Hz), residual fp64 (field fit only, else
+    None) and status int32 (0 done, 1 window end, 2 non-finite, 3 all-zero row, 4 step cap).  `copied`: whether the
+    layout needed the one contiguous copy; `levels`: the (row, column) index levels the kernel addressed."""
+
+    __slots__ = ("species", "field", "residual", "status", "copied", "levels")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+SPECIES_MAX_ECHOES = 32
+SPECIES_MAX_ECHOES_FIT = 16
+SPECIES_MAX_SPECIES = 8
+SPECIES_MAX_GRID = 1025
+SPECIES_SKIP = {"gram": _lib.XM_SPECIES_SKIP_GRAM, "coarse": _lib.XM_SPECIES_SKIP_COARSE,
+                "refine": _lib.XM_SPECIES_SKIP_REFINE, "apply": _lib.XM_SPECIES_SKIP_APPLY}
+
+
+def species_grid(echo_times, max_field: float):
+    """(delta, G) of the coarse grid of the field fit: delta = 1 / (4 (max TE - min TE)), G = floor(max_field / delta)."""
+    te = np.asarray(echo_times, dtype=np.float64)
+    delta = 1.0 / (4.0 * float(te.max() - te.min()))
+    return delta, int(np.floor(max_field / delta))
+
+
+def species_tables(echo_times, frequencies, decay=None, fit: bool = False):
+    """Host fp64 tables of xm_species_separate as one flat array: TE[E], f[M], R[M], P0 = pinv(A0) as (re, im), and with
+    `fit` the diagonal of Pi = Q Q^H (Q from the QR of A0) and Pi[e', e] for the pairs e < e' in ascending order."""
+    te = np.asarray(echo_times, dtype=np.float64).reshape(-1)
+    f = np.asarray(frequencies, dtype=np.float64).reshape(-1)
+    r = np.zeros_like(f) if decay is None else np.asarray(decay, dtype=np.float64).reshape(-1)
+    a0 = np.exp((2j * np.pi * f - r)[None, :] * te[:, None])
+    p0 = np.linalg.pinv(a0)
+    parts = [te, f, r, np.stack([p0.real, p0.imag], axis=-1).reshape(-1)]
+    if fit:
+        q = np.linalg.qr(a0)[0]
+        pi = q @ q.conj().T
+        iu = np.triu_indices(len(te), 1)  # (e, e') ascending, e < e'
+        low = pi[iu[1], iu[0]]
+        parts += [np.diagonal(pi).real, np.stack([low.real, low.imag], axis=-1).reshape(-1)]
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+_SPECIES_TABLES = {}  # (device, fit, the model's bytes) -> the tables in HBM; a handful of models per session
+
+
+def _species_tables_on(device, te, f, r, fit: bool):
+    """`species_tables` uploaded once per model and device (the upload is a blocking copy: not one per call)."""
+    torch = _torch()
+    r = np.zeros_like(np.asarray(f, dtype=np.float64).reshape(-1)) if r is None else np.asarray(r, dtype=np.float64).reshape(-1)
+    key = (str(device), bool(fit), te.tobytes(), np.asarray(f, dtype=np.float64).tobytes(), r.tobytes())
+    t = _SPECIES_TABLES.get(key)
+    if t is None:
+        if len(_SPECIES_TABLES) >= 32:
+            _SPECIES_TABLES.clear()
+        t = _SPECIES_TABLES[key] = torch.from_numpy(species_tables(te, f, r, fit)).to(device)
+    return t
+
+
+def _collapse(sizes, strides):
+    """Index levels of axes given outermost first: `strides` lists, per axis, its stride in every array that is
+    addressed (x, y, tau, psi).  Axes of size 1 drop out; neighbours merge when in every array the outer stride is the
+    inner one times the inner size.  Returns [(size, strides), ...]."""
+    out = []
+    for n, st in zip(sizes, strides):
+        if n == 1:
+            continue
+        if out and all(a == b * n for a, b in zip(out[-1][1], st)):
+            out[-1] = (out[-1][0] * n, tuple(st))
+        else:
+            out.append((n, tuple(st)))
+    return out
+
+
+def species_separate(x, echo_axis: int, col_axes, echo_times, frequencies, decay=None, tau=None, psi=None,
+                     fit_field: bool = False, max_field=None, _skip=()) -> SpeciesResult:
+    """Least-squares separation of M chemical species from the E echoes of the complex64 / complex128 device tensor `x`
+    in one launch of k_species (xm_species_separate).  `col_axes`: the axes that share a row's
+    readout delay and field offset (coils); every axis that is neither `echo_axis` nor a column axis is a row axis.
+    `tau` (s) and `psi` (Hz): None, or fp64 values that broadcast against the row axes in the input's order.
+    `fit_field`: psi is fitted per row within +-`max_field` Hz from all columns of the row.  The tensor is addressed
+    where it lies whenever the row axes collapse into at most two strided index levels and the column axes into at
+    most two; any other layout costs one contiguous copy with the rows in front (`copied` on the result says which).
+    `_skip` (tests and timing only): stages to leave out, of "gram", "coarse", "refine", "apply"."""
+    torch = _torch()
+    _require_device(x)
+    code = _dtype_code(x)
+    nd = x.dim()
+    ea = echo_axis % nd
+    cols = [a % nd for a in col_axes]
+    if ea in cols or len(set(cols)) != len(cols):
+        raise ValueError("col_axes must be distinct axes other than echo_axis")
+    rows = [a for a in range(nd) if a != ea and a not in cols]
+    cols = sorted(cols)
+    te = np.asarray(echo_times, dtype=np.float64).reshape(-1)
+    E, M = x.shape[ea], int(np.size(frequencies))
+    if len(te) != E:
+        raise ValueError(f"echo_times: {len(te)} values for {E} echoes")
+    if fit_field and psi is not None:
+        raise ValueError("psi and fit_field exclude each other")
+    tables = _species_tables_on(x.device, te, frequencies, decay, bool(fit_field))
+    row_shape = tuple(x.shape[a] for a in rows)
+    oshape = tuple(M if a == ea else x.shape[a] for a in range(nd))
+    y = torch.empty(oshape, dtype=x.dtype, device=x.device)
+    field = torch.empty(row_shape, dtype=torch.float64, device=x.device)
+    status = torch.empty(row_shape, dtype=torch.int32, device=x.device)
+    residual = torch.empty(row_shape, dtype=torch.float64, device=x.device) if fit_field else None
+
+    def per_row(v):
+        if v is None:
+            return None
+        if not isinstance(v, torch.Tensor):
+            v = torch.from_numpy(np.asarray(v, dtype=np.float64))
+        v = v.to(device=x.device, dtype=torch.float64)
+        return torch.broadcast_to(v, row_shape)
+
+    tau_t, psi_t = per_row(tau), per_row(psi)
+
+    def levels(xs, ys, tt, pt):
+        per = [t_ for t_ in (tt, pt) if t_ is not None]
+        rl = _collapse(row_shape, [[xs.stride(a), ys.stride(a)] + [t_.stride(i) for t_ in per] for i, a in enumerate(rows)])
+        cl = _collapse([xs.shape[a] for a in cols], [[xs.stride(a), ys.stride(a)] for a in cols])
+        return rl, cl, per
+
+    rl, cl, per = levels(x, y, tau_t, psi_t)
+    if len(rl) > 2 and per:  # the per-row values in the rows' own order: they then merge wherever x does
+        tau_t = tau_t.contiguous() if tau_t is not None else None
+        psi_t = psi_t.contiguous() if psi_t is not None else None
+        rl, cl, per = levels(x, y, tau_t, psi_t)
+    xs, ys, copied = x, y, False
+    if len(rl) > 2 or len(cl) > 2:  # one contiguous copy: rows, echo, columns
+        order = rows + [ea] + cols
+        xs = x.permute(order).contiguous()
+        ys = torch.empty(tuple(oshape[a] for a in order), dtype=x.dtype, device=x.device)
+        inv = [order.index(a) for a in range(nd)]
+        xs, ys, copied = xs.permute(inv), ys.permute(inv), True  # the input's axis numbering, the copy's strides
+        tau_t = tau_t.contiguous() if tau_t is not None else None
+        psi_t = psi_t.contiguous() if psi_t is not None else None
+        rl, cl, per = levels(xs, ys, tau_t, psi_t)
+    rl = [(1, (0,) * (2 + len(per)))] * (2 - len(rl)) + rl
+    cl = [(1, (0, 0))] * (2 - len(cl)) + cl
+    i64 = lambda *v: (ctypes.c_int64 * len(v))(*[int(q) for q in v])  # noqa: E731
+    dims = i64(rl[0][0], rl[1][0], cl[0][0], cl[1][0])
+    xst = i64(rl[0][1][0], rl[1][1][0], cl[0][1][0], cl[1][1][0], xs.stride(ea))
+    yst = i64(rl[0][1][1], rl[1][1][1], cl[0][1][1], cl[1][1][1], ys.stride(ea))
+    k = 2
+    ts = ps = (0, 0)
+    if tau_t is not None:
+        ts, k = (rl[0][1][k], rl[1][1][k]), k + 1
+    if psi_t is not None:
+        ps = (rl[0][1][k], rl[1][1][k])
+    span = float(te.max() - te.min()) if E else 0.0
+    for s in _skip:
+        code |= SPECIES_SKIP[s]
+    ptr = lambda t_: t_.data_ptr() if t_ is not None else None  # noqa: E731
+    _lib.call("xm_species_separate", xs.data_ptr(), ys.data_ptr(), dims, xst, yst, E, M, tables.data_ptr(), ptr(tau_t),
+              ts[0], ts[1], ptr(psi_t), ps[0], ps[1], field.data_ptr(), ptr(residual), status.data_ptr(),
+              1 if fit_field else 0, float(max_field) if fit_field else 0.0, span, code, _stream(x))
+    if copied:
+        y.copy_(ys)
+    return SpeciesResult(species=y, field=field, residual=residual, status=status, copied=copied,
+                         levels=(sum(n > 1 for n, _ in rl), sum(n > 1 for n, _ in cl)))
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 

@@ -12,13 +12,15 @@ from .mrsi import to_image, to_kspace
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
 from .phasing import autophase, autophase_each, phase
 from .sense import sense_maps, unfold_sense
+from .species import separate_species, simulate_echoes, species_matrix
 from .timeshift import correct_readout_time, readout_offsets, shift_time
 from .water import remove_water
 
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense",
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense",
-           "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps"]
+           "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
+           "separate_species", "simulate_echoes", "species_matrix"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled
