@@ -497,6 +497,43 @@ int xm_cgs_step(void* x, void* r, const void* p, const void* q, const double* rh
                 const double* delta, double* rho_out, const int32_t* status_in, int32_t* status_out, int32_t* n_iter,
                 double* residual, int64_t n_vox, int64_t n_cols, double tol, int iteration, int final_test, void* stream);
 
+/* ---- Wavelet-sparse SENSE: the image-sized half of a proximal-gradient (FISTA) step (this
+ * backend's own definition, the reference has none).  The image has n_dims <= 3 dims of m_0 x m_1 x m_2 voxels in C order
+ * (a dim beyond n_dims: size 1, level 0, shift 0), V their product, and T = n_cols independent columns; x, v, q, b [V, T]
+ * complex128, mask [V] bytes, all C-contiguous in device memory.  The image is cut into blocks of 2^l_d voxels per dim,
+ * B = 2^(l_0 + l_1 + l_2) <= 16, on a lattice moved by the shift s_d (0 <= s_d < 2^l_d) with periodic wrap: block
+ * (n_0, n_1, n_2) holds the voxels ((n_d << l_d) + i_d + s_d) mod m_d; NBL = V / B blocks, numbered in C order.  Each
+ * block is transformed by the orthonormal decimated Haar transform of l_d levels per dim: dims ascending, levels fine to
+ * coarse, every butterfly (a + b) r, (a - b) r with r = 1 / sqrt(2).  A sum over voxels is kept as partials [NBL, T] fp64
+ * (per block in ascending in-block index i_0 + (i_1 << l_0) + (i_2 << (l_0 + l_1))), a total is the sum of a column's
+ * partials in ascending block order.
+ *   xm_l1_start, finish == 0: bpart[r, t] = max |b[v, t]|^2 over the 16 consecutive voxels of run r (bpart: [ceil(V / 16),
+ *     T] fp64; the other pointers are not used and may be NULL).  finish != 0: bmax[t] = sqrt(max_r bpart[r, t]) and
+ *     status[t] = 0; where that maximum is not finite, status[t] = 3, bmax[t] = change[t] = NaN and x[:, t] = NaN (b is not
+ *     used and may be NULL).
+ *   xm_l1_prox, for a column with status_in[t] == 0.  Unless mode == 1, first the test on the totals d2, n2 of d2_in and
+ *     n2_in: either not finite -> status 3 and x[:, t] = NaN; d2 <= tol^2 n2 -> status 1; mode == 2 (final test) -> status
+ *     stays 0 and nothing else happens.  Otherwise the step:  w = v - tau (q - b)  (mode == 1, the first step: q is taken
+ *     as 0 and, like d2_in and n2_in, may be NULL),  c = Haar(w),  every coefficient but the one at in-block index 0 (with
+ *     B = 1: every coefficient) becomes c max(0, 1 - theta / |c|) with theta = theta_scale bmax[t],  x' = mask ? Haar^-1(c)
+ *     : 0,  v <- x' + beta (x' - x),  x <- x',  d2_out[n, t] = sum |x' - x|^2 and n2_out[n, t] = sum |x'|^2 over block n,
+ *     n_iter[t] = iteration.  status_out[t] is written for every column; change[t] = sqrt(d2 / n2) (0 for d2 = 0, NaN
+ *     with status 3) for a column that leaves status 0 in this call, and in a final test for one that stays 0.  A column
+ *     with status_in[t] != 0 is not touched.
+ * No call reads a per-column value that the same call writes (the caller alternates two buffers for the partials and for
+ * status), there are no atomics, and a column depends on its own values only: results are bitwise independent of the
+ * other columns of the call.  n_dims in 1 ... 3, every m_d, V and T in 1 ... 2^31 - 1, at most 2^50 elements, m_d divisible
+ * by 2^l_d, B <= 16, a shift inside its block, tau, theta_scale, beta and tol finite and >= 0, iteration >= 0, mode in
+ * 0 ... 2, non-NULL pointers aligned to their element size, no output equal to an input or to another output: otherwise
+ * XM_ERR_INVALID_ARG before any HIP call. */
+int xm_l1_start(const void* b, double* bpart, double* bmax, int32_t* status, double* change, void* x, int64_t n_vox,
+                int64_t n_cols, int finish, void* stream);
+int xm_l1_prox(void* x, void* v, const void* q, const void* b, const uint8_t* mask, const double* bmax,
+               const double* d2_in, const double* n2_in, double* d2_out, double* n2_out, const int32_t* status_in,
+               int32_t* status_out, int32_t* n_iter, double* change, int n_dims, int64_t m0, int64_t m1, int64_t m2, int l0,
+               int l1, int l2, int s0, int s1, int s2, int64_t n_cols, double tau, double theta_scale, double beta, double tol,
+               int iteration, int mode, void* stream);
+
 /* ---- ESPIRiT: per-voxel eigen-decomposition of a coil x coil Hermitian matrix (this backend's own
  * definition, the reference has none).  h: [n_vox, E] complex128, E = C (C + 1) / 2, C = n_coils: per voxel the upper
  * triangle (i <= j) of its matrix in row-major order; the lower triangle is the conjugate and the imaginary part of the

@@ -14,7 +14,7 @@ from .fitting import basis_model, fit_amares, fit_basis, fit_kinetics, simulate_
 from .fused import spectral_pipeline
 from .labeled import Coordinate, LabeledArray
 from .vendor.bruker import remove_digital_filter
-from .processing import (align_averages, baseline_als, combine_coils, degrid_kspace, denoise_mppca, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward, recon_cg_sense, apodize_exp, apodize_lg, autophase, autophase_each, fft, fftc, fftshift, ifft, ifftc, ifftshift, phase,
+from .processing import (align_averages, baseline_als, combine_coils, degrid_kspace, denoise_mppca, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward, recon_cg_sense, recon_l1_sense, apodize_exp, apodize_lg, autophase, autophase_each, fft, fftc, fftshift, ifft, ifftc, ifftshift, phase,
                          remove_water, sense_maps, to_fid, to_image, to_kspace, to_spectrum, unfold_sense, zero_fill,
                          correct_readout_time, readout_offsets, shift_time, GrappaWeights, grappa_calibrate, grappa_fill, espirit_maps,
                          separate_species, simulate_echoes, species_matrix)
@@ -25,7 +25,7 @@ register_xarray_accessor()  # no-op when xarray is absent or the name `xmr` is a
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "ATTRS", "COORDS", "DIMS", "Coordinate", "DataArray", "LabeledArray", "XmrisAccessor",
            "apodize_exp", "apodize_lg", "autophase", "autophase_each", "basis_model", "fft", "fit_amares", "fit_basis", "fftc", "fftshift", "ifft", "ifftc", "ifftshift",
            "phase", "register_xarray_accessor", "remove_digital_filter", "remove_water", "sense_maps", "simulate_fid", "spectral_pipeline", "to_fid", "to_image", "to_kspace", "to_spectrum", "unfold_sense", "zero_fill",
-           "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense",
+           "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense", "recon_l1_sense",
            "shift_time", "correct_readout_time", "readout_offsets", "fit_kinetics", "simulate_kinetics",
            "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
            "separate_species", "simulate_echoes", "species_matrix"]

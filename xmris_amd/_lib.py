@@ -49,6 +49,7 @@ XM_SPECIES_SKIP_APPLY = 0x800
 
 XM_SENSE_WORKSPACE_BYTES = 256
 XM_CGS_VOXELS = 16
+XM_L1_MAX_BLOCK = 16
 
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
@@ -106,6 +107,9 @@ SIGNATURES = {
     "xm_cgs_expand": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _i, _i, _p]),
     "xm_cgs_reduce": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, ctypes.c_double, _i, _i, _p]),
     "xm_cgs_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, ctypes.c_double, _i, _i, _p]),
+    "xm_l1_start": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _i, _p]),
+    "xm_l1_prox": (_i, [_p] * 14 + [_i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, ctypes.c_double, _i, _i, _p]),
     "xm_espirit_eig": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, ctypes.c_double, _p]),
     "xm_shift_time_fused": (_i, [_i, _i]),
     "xm_shift_time": (_i, [_p, _l, _p, _l, _i, _i, _p, _l, _l, _i, _p]),

@@ -189,6 +189,23 @@ class XmrisMrsiMixin:
                               oversampling=oversampling, width=width, dim=dim, coil_dim=coil_dim, out_dim=out_dim, fov=fov,
                               readout_time=readout_time, chunk=chunk, return_info=return_info)
 
+    def recon_l1_sense(self, trajectory, sensitivities, matrix=None, sparsity: float = 0.02, levels=None, iterations: int = 50,
+                       tol: float = 1e-4, tikhonov: float = 0.0, cycle_spin: bool = False, step=None,
+                       power_iterations: int = 20, step_safety=None, density=None, noise_cov=None, oversampling: float = 2.0,
+                       width: int = 4, dim: str = DIMS.sample, coil_dim: str = DIMS.coil, out_dim=None, fov=1.0,
+                       readout_time=None, chunk=None, return_info: bool = False):
+        """Wavelet-sparse iterative SENSE of multi-coil, undersampled, non-Cartesian samples: FISTA with a blockwise
+        Haar l1 penalty around the two NUFFT chains, every column on its own (an addition of this backend; DESIGN.md
+        section 24)."""
+        from .processing.l1sense import STEP_SAFETY, recon_l1_sense
+
+        return recon_l1_sense(self._obj, trajectory, sensitivities, matrix=matrix, sparsity=sparsity, levels=levels,
+                              iterations=iterations, tol=tol, tikhonov=tikhonov, cycle_spin=cycle_spin, step=step,
+                              power_iterations=power_iterations, step_safety=STEP_SAFETY if step_safety is None else step_safety,
+                              density=density, noise_cov=noise_cov, oversampling=oversampling, width=width, dim=dim,
+                              coil_dim=coil_dim, out_dim=out_dim, fov=fov, readout_time=readout_time, chunk=chunk,
+                              return_info=return_info)
+
     def espirit_maps(self, matrix, kernel=None, dims=(DIMS.kx, DIMS.ky), coil_dim: str = DIMS.coil,
                      time_dim: str = DIMS.time, acs_points: int = 8, threshold: float = 0.02, crop: float = 0.8,
                      n_maps: int = 1, noise_cov=None, phase_ref: int = 0, return_eigenvalues: bool = False):

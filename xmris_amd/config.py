@@ -83,6 +83,12 @@ class _Attrs(_Vocabulary):
     cgsense_iterations = XmrisTerm("cgsense_iterations", "Iteration cap of the CG-SENSE reconstruction.")
     cgsense_tol = XmrisTerm("cgsense_tol", "Relative residual at which a column of the CG-SENSE reconstruction stops.")
     cgsense_regularization = XmrisTerm("cgsense_regularization", "Tikhonov weight of the CG-SENSE reconstruction, relative to the mean diagonal of the normal matrix.")
+    l1sense_sparsity = XmrisTerm("l1sense_sparsity", "Weight of the wavelet l1 penalty of the sparse SENSE reconstruction, relative to the largest |E^H D y| of the column.")
+    l1sense_levels = XmrisTerm("l1sense_levels", "Haar levels per image dimension of the sparse SENSE reconstruction.")
+    l1sense_iterations = XmrisTerm("l1sense_iterations", "Iteration cap of the sparse SENSE reconstruction.")
+    l1sense_tol = XmrisTerm("l1sense_tol", "Relative change of the image at which a column of the sparse SENSE reconstruction stops.")
+    l1sense_step = XmrisTerm("l1sense_step", "Step size of the proximal iteration of the sparse SENSE reconstruction.")
+    l1sense_lipschitz = XmrisTerm("l1sense_lipschitz", "Lipschitz bound of the smooth part that the step size of the sparse SENSE reconstruction comes from.")
     time_shift_pad_to = XmrisTerm("time_shift_pad_to", "Transform length of the last time shift along the FID axis.")
     readout_time_corrected = XmrisTerm("readout_time_corrected", "Whether the acquisition delays of the readout's samples have been removed.")
     kinetics_model = XmrisTerm("kinetics_model", "Rate model that fit_kinetics fitted along the repetitions.")

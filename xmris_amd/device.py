@@ -12,6 +12,7 @@ kernels see ``[n_batch, n]`` C-contiguous rows, and moved back afterwards, exact
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -1252,6 +1253,155 @@ def cg_sense(y, s, adjoint, forward, lam: float, iterations: int, tol: float) ->
     cgs_step(x, r, p, q, rho0 if n == 0 else rho[n % 2], rho0, None, rho[(n + 1) % 2], status[n % 2], status[(n + 1) % 2],
              n_iter, residual, tol, n, final=True)
     return CgSense(x=x, residual=residual, iterations=n_iter, status=status[(n + 1) % 2])
+
+
+L1_MAX_BLOCK = _lib.XM_L1_MAX_BLOCK
+
+
+def l1_blocks(matrix, levels) -> int:
+    """Haar blocks, i.e. partials per column, of k_l1_prox."""
+    return int(np.prod([int(m) >> int(l) for m, l in zip(matrix, levels)], dtype=np.int64))
+
+
+def _l1_three(values, fill: int):
+    values = [int(a) for a in values]
+    return values + [fill] * (3 - len(values))
+
+
+def l1_start(b, x, bmax, status, change):
+    """The two launches of k_l1_start (xm_l1_start): ``bmax[t] = max_v |b[v, t]|`` and ``status[t] =
+    0``; a column whose maximum is not finite gets status 3, a NaN `bmax` and `change` and a NaN column of `x`.
+    b, x: [V, T] complex128; bmax, change: [T] fp64; status: [T] int32."""
+    torch = _torch()
+    v, t = (int(n) for n in b.shape)
+    _cgs_c128(b, (v, t), "b"), _cgs_c128(x, (v, t), "x")
+    _cgs_plain(bmax, torch.float64, (t,), "bmax"), _cgs_plain(change, torch.float64, (t,), "change")
+    _cgs_plain(status, torch.int32, (t,), "status")
+    part = torch.empty(((v + L1_MAX_BLOCK - 1) // L1_MAX_BLOCK, t), dtype=torch.float64, device=b.device)
+    _lib.call("xm_l1_start", b.data_ptr(), part.data_ptr(), None, None, None, None, v, t, 0, _stream(b))
+    _lib.call("xm_l1_start", None, part.data_ptr(), bmax.data_ptr(), status.data_ptr(), change.data_ptr(), x.data_ptr(), v, t,
+              1, _stream(b))
+
+
+def l1_prox(x, v, q, b, mask, bmax, d2_in, n2_in, d2_out, n2_out, status_in, status_out, n_iter, change, matrix, levels,
+            shift, tau: float, theta_scale: float, beta: float, tol: float, iteration: int, mode: int = 0):
+    """One launch of k_l1_prox (xm_l1_prox): per column whose `status_in` is 0 the stopping test on the totals of `d2_in`,
+    `n2_in` and, where it does not hold, ``w = v - tau (q - b)``, the blockwise Haar transform of `levels` on the lattice
+    moved by `shift`, the shrink of the detail coefficients by ``theta_scale bmax``, the transform back, the mask, ``v <-
+    x' + beta (x' - x)``, ``x <- x'`` and the partials of ``|x' - x|^2`` and ``|x'|^2``.  `mode`: 0 a step, 1 the first
+    step (no test; q, d2_in and n2_in may be None), 2 the final test alone.  x, v, q, b: [V, T] complex128, V the product of
+    `matrix`; mask: [V] uint8; bmax, change: [T] fp64; the partials: [l1_blocks, T] fp64; status_in, status_out, n_iter: [T]
+    int32."""
+    torch = _torch()
+    vox, t = (int(n) for n in x.shape)
+    if int(np.prod(matrix, dtype=np.int64)) != vox or not len(matrix) == len(levels) == len(shift) or not 1 <= len(matrix) <= 3:
+        raise ValueError(f"matrix {tuple(matrix)}, levels {tuple(levels)} and shift {tuple(shift)} do not describe the {vox} voxels of x")
+    nb = l1_blocks(matrix, levels)
+    first = mode == 1
+    for a, name in ((x, "x"), (v, "v"), (b, "b")) + (() if first else ((q, "q"),)):
+        _cgs_c128(a, (vox, t), name)
+    for a, name in ((d2_out, "d2_out"), (n2_out, "n2_out")) + (() if first else ((d2_in, "d2_in"), (n2_in, "n2_in"))):
+        _cgs_plain(a, torch.float64, (nb, t), name)
+    for a, name in ((status_in, "status_in"), (status_out, "status_out"), (n_iter, "n_iter")):
+        _cgs_plain(a, torch.int32, (t,), name)
+    _cgs_plain(bmax, torch.float64, (t,), "bmax"), _cgs_plain(change, torch.float64, (t,), "change")
+    _cgs_plain(mask, torch.uint8, (vox,), "mask")
+    ptr = lambda a: None if a is None else a.data_ptr()  # noqa: E731
+    _lib.call("xm_l1_prox", x.data_ptr(), v.data_ptr(), None if first else q.data_ptr(), b.data_ptr(), mask.data_ptr(),
+              bmax.data_ptr(), None if first else ptr(d2_in), None if first else ptr(n2_in), d2_out.data_ptr(),
+              n2_out.data_ptr(), status_in.data_ptr(), status_out.data_ptr(), n_iter.data_ptr(), change.data_ptr(),
+              len(matrix), *_l1_three(matrix, 1), *_l1_three(levels, 0), *_l1_three(shift, 0), t, float(tau),
+              float(theta_scale), float(beta), float(tol), int(iteration), int(mode), _stream(x))
+
+
+def fista_momentum(iterations: int):
+    """beta_k = (t_k - 1) / t_{k+1} with t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2, k = 0 ... iterations - 1."""
+    out, tk = [], 1.0
+    for _ in range(int(iterations)):
+        nxt = (1.0 + math.sqrt(1.0 + 4.0 * tk * tk)) / 2.0
+        out.append((tk - 1.0) / nxt)
+        tk = nxt
+    return out
+
+
+def l1_lipschitz(s, adjoint, forward, mask, power_iterations: int, dtype) -> float:
+    """The Rayleigh quotient of ``E^H D E`` after `power_iterations` power steps from the mask indicator, on one column
+    through the launches of the iteration: k_cgs_expand (first) gives u = s v, the two chains, k_cgs_reduce gives q and
+    Re<v, q>.  Set-up: the host reads the scalars of every step.  s: [C, V] complex128; mask: [V] uint8; `dtype`: that of
+    the coil-sized arrays."""
+    torch = _torch()
+    _require_device(s)
+    c, v = (int(n) for n in s.shape)
+    nb = cgs_blocks(v)
+    vec = mask.to(torch.complex128).reshape(v, 1).contiguous()
+    norm = float(torch.linalg.vector_norm(vec))
+    if not norm > 0.0:
+        return 0.0
+    vec = vec / norm
+    p, q = torch.zeros_like(vec), torch.empty_like(vec)
+    part = torch.zeros((nb, 1), dtype=torch.float64, device=s.device)
+    live = torch.zeros(1, dtype=torch.int32, device=s.device)
+    for k in range(int(power_iterations) + 1):
+        u = cgs_expand(vec, p, s, part, part, live, True, dtype)
+        cgs_reduce(adjoint(forward(u)).reshape(c, v, 1), s, p, q, part, 0.0)
+        quotient = float(part.sum())
+        norm = float(torch.linalg.vector_norm(q))
+        if k == power_iterations or not norm > 0.0 or not math.isfinite(norm):
+            break
+        vec = q / norm
+    return quotient
+
+
+class L1Sense:
+    """Raw outputs of ``l1_sense``: x [V, T] complex128; change [T] fp64 (sqrt(d2 / n2) at the last test of the column);
+    iterations [T] int32; status [T] int32 (0 iteration cap, 1 converged, 3 not finite: x is NaN)."""
+
+    __slots__ = ("x", "change", "iterations", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def l1_sense(y, s, adjoint, forward, mask, matrix, levels, lam2: float, sparsity: float, tau: float, iterations: int,
+             tol: float, cycle_spin: bool = False) -> L1Sense:
+    """FISTA on ``1/2 |D^(1/2) (E x - y)|^2 + lam2 / 2 |x|^2 + sparsity max|b| |Psi x|_1`` from x = 0, every column on its
+    own.  y, s, `adjoint`, `forward` as in `cg_sense`; mask: [V] uint8; `tau`: the step 1 / L.
+    Queues a fixed sequence of launches -- per step k_cgs_expand (first), the two chains, k_cgs_reduce and k_l1_prox; the
+    first step has the prox alone -- and reads nothing back."""
+    torch = _torch()
+    _require_device(y)
+    c, v = (int(n) for n in s.shape)
+    t = int(y.shape[2])
+    dev_ = y.device
+    nb = l1_blocks(matrix, levels)
+    c128 = dict(dtype=torch.complex128, device=dev_)
+    f64 = dict(dtype=torch.float64, device=dev_)
+    x, vk, p = (torch.zeros((v, t), **c128) for _ in range(3))
+    b, q = (torch.empty((v, t), **c128) for _ in range(2))
+    scratch = torch.empty((cgs_blocks(v), t), **f64)  # the partials of k_cgs_reduce, which nothing here reads
+    d2, n2 = (torch.empty((2, nb, t), **f64) for _ in range(2))
+    status = torch.zeros((2, t), dtype=torch.int32, device=dev_)
+    n_iter = torch.zeros(t, dtype=torch.int32, device=dev_)
+    bmax, change = (torch.zeros(t, **f64) for _ in range(2))
+
+    cgs_reduce(adjoint(y).reshape(c, v, t), s, None, b, scratch, initial=True)
+    l1_start(b, x, bmax, status[0], change)
+    n = int(iterations)
+    zero = [0] * len(matrix)
+    for k, beta in enumerate(fista_momentum(n)):
+        now, nxt = k % 2, (k + 1) % 2
+        if k:
+            u = cgs_expand(vk, p, s, scratch, scratch, status[now], True, y.dtype)
+            cgs_reduce(adjoint(forward(u)).reshape(c, v, t), s, p, q, scratch, lam2)
+        shift = [k % (1 << int(l)) for l in levels] if cycle_spin else zero
+        l1_prox(x, vk, q, b, mask, bmax, d2[now], n2[now], d2[nxt], n2[nxt], status[now], status[nxt], n_iter, change,
+                matrix, levels, shift, tau, tau * sparsity, beta, tol, k + 1, 1 if k == 0 else 0)
+    if n == 0:
+        return L1Sense(x=x, change=change, iterations=n_iter, status=status[0])
+    l1_prox(x, vk, q, b, mask, bmax, d2[n % 2], n2[n % 2], d2[(n + 1) % 2], n2[(n + 1) % 2], status[n % 2],
+            status[(n + 1) % 2], n_iter, change, matrix, levels, zero, tau, tau * sparsity, 0.0, tol, n, 2)
+    return L1Sense(x=x, change=change, iterations=n_iter, status=status[(n + 1) % 2])
 
 
 class EspiritEig:

@@ -7,6 +7,7 @@ from .espirit import espirit_maps
 from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .grappa import GrappaWeights, grappa_calibrate, grappa_fill
 from .cgsense import recon_cg_sense
+from .l1sense import recon_l1_sense
 from .grid import degrid_kspace, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward
 from .mrsi import to_image, to_kspace
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
@@ -18,7 +19,7 @@ from .water import remove_water
 
 __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "apodize_exp", "apodize_lg", "to_fid", "to_spectrum", "zero_fill", "fft", "fftc", "fftshift", "ifft",
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense",
-           "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense",
+           "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense", "recon_l1_sense",
            "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
            "separate_species", "simulate_echoes", "species_matrix"]
 

@@ -87,6 +87,155 @@ def normal_scale(sens_abs2_sum, weights, n_vox: int) -> float:
     return float(np.sum(weights) / n_vox) * float(live.mean())
 
 
+class _Problem:
+    """What ``recon_cg_sense`` and ``recon_l1_sense`` share: the data as [C, S, T] in its dtype, the (whitened) maps [C, V]
+    complex128 and their energy per voxel, the gridding table, the two chains on raw tensors, and what the result's
+    dims, coordinates and attrs are made from."""
+
+
+def _columns(chunk):
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1):
+        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
+
+
+def _problem(who: str, da, trajectory, sensitivities, matrix, density, noise_cov, oversampling, width, dim, coil_dim, out_dim,
+             fov, readout_time) -> _Problem:
+    """Validates everything that describes the acquisition (before the library is reached) and uploads maps and tables
+    once."""
+    pb = _Problem()
+    src0 = as_labeled(da)
+    _check_dims(src0, (dim, coil_dim), who)
+    if dim == coil_dim:
+        raise ValueError(f"coil_dim: {coil_dim!r} is the sample dim")
+    c = src0.sizes[coil_dim]
+    if not 1 <= c <= MAX_COILS:
+        raise ValueError(f"coil_dim: {c} coils along {coil_dim!r}, supported are 1 ... {MAX_COILS}")
+    k = _trajectory(trajectory)
+    d = k.shape[1]
+    if k.shape[0] != src0.sizes[dim]:
+        raise ValueError(f"trajectory: {k.shape[0]} samples for a {dim!r} dim of {src0.sizes[dim]} points")
+    sens, spatial = _sens(sensitivities, coil_dim, d, c)
+    if matrix is not None:
+        mat = _per_dim(matrix, d, "matrix", _int)
+        if mat is None or tuple(mat) != tuple(spatial):
+            raise ValueError(f"matrix: {matrix!r} disagrees with the sensitivities' spatial shape {tuple(spatial)}")
+    rest = [n for n in src0.dims if n not in (dim, coil_dim)]
+    names = _names(out_dim, d, X_DIMS, "out_dim", rest)
+    f = _fov(fov, d)
+    linv = None if noise_cov is None else _linv(noise_cov, c)
+    t = grid_table(k, spatial, oversampling, width, density)
+    pb.da, pb.dim, pb.coil_dim, pb.density = da, dim, coil_dim, density
+    pb.c, pb.spatial, pb.rest, pb.names, pb.fov, pb.table = c, tuple(spatial), rest, names, f, t
+    pb.sens, pb.linv = sens, linv
+    return pb
+
+
+def _upload(pb: _Problem, readout_time) -> _Problem:
+    """The second half of the set-up, which reaches the library: the data in the order (coil, sample, columns), the maps
+    and the tables on the device, the whitening."""
+    da, dim, coil_dim, c, spatial, rest, t, sens, linv = (pb.da, pb.dim, pb.coil_dim, pb.c, pb.spatial, pb.rest, pb.table,
+                                                          pb.sens, pb.linv)
+    da_t = _readout(da, readout_time, dim, False)
+    src = as_labeled(da_t)
+    y, _ = device_data(src)
+    on_device = hasattr(y, "detach")
+    perm = [src.get_axis_num(coil_dim), src.get_axis_num(dim)] + [src.get_axis_num(n) for n in rest]
+    if perm != list(range(src.ndim)):
+        y = y.permute(perm) if on_device else np.transpose(y, perm)
+    cols = tuple(int(n) for n in y.shape[2:])
+    n_samples, n_cols, n_vox = int(len(t.density)), int(np.prod(cols, dtype=np.int64)), int(np.prod(spatial))
+    if n_cols < 1:
+        raise ValueError(f"da: an empty dimension among {tuple(rest)}")
+    y = y.reshape(c, n_samples, n_cols)
+    y = y.contiguous() if on_device else np.ascontiguousarray(y)
+
+    # the maps: complex128 on the device, [C, V]; whitening is one axis_dft along the coil axis of maps and data
+    if on_device:
+        import torch
+
+        s = (sens if hasattr(sens, "detach") else torch.from_numpy(np.array(sens, dtype=np.complex128, order="C")))
+        s = s.to(device=y.device, dtype=torch.complex128).reshape(c, n_vox).contiguous()
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.complex128)).to(y.device)  # noqa: E731
+    else:
+        s = np.array(sens, dtype=np.complex128, order="C").reshape(c, n_vox)
+        up = lambda a: np.ascontiguousarray(a, dtype=np.complex128)  # noqa: E731
+    if linv is not None:
+        white = up(linv)
+        s = dev.axis_dft(s, 0, white)
+        y = dev.axis_dft(y, 0, white)
+    energy = s.real ** 2 + s.imag ** 2
+    energy = energy.sum(dim=0).cpu().numpy() if on_device else energy.sum(axis=0)
+
+    # the tables of both chains go up once; SparseTable keeps its own device copy
+    to_voxels, to_samples = [up(a) for a in _image_tables(t, 1.0)], [up(a) for a in _image_tables(t, -1.0)]
+
+    def adjoint(v):  # [C, S, T] -> [C, V, T]
+        g = dev.axis_sparse(v, 1, t.grid)
+        return _to_voxels(g, 1, t, to_voxels).reshape(c, n_vox, v.shape[2])
+
+    def forward(u):  # [C, V, T] -> [C, S, T]
+        return _to_samples(u.reshape((c,) + tuple(spatial) + (u.shape[2],)), 1, t, to_samples)
+
+    pb.src, pb.y, pb.s, pb.energy, pb.on_device, pb.cols = src, y, s, energy, on_device, cols
+    pb.n_cols, pb.n_vox, pb.adjoint, pb.forward = n_cols, n_vox, adjoint, forward
+    return pb
+
+
+def _passes(pb: _Problem, chunk, run):
+    """``run(columns of y)`` per pass of `chunk` columns (default: `default_chunk`)."""
+    y, n_cols, on_device = pb.y, pb.n_cols, pb.on_device
+    step = default_chunk(pb.c, pb.table.oversampled, y.dtype.itemsize if not on_device else y.element_size(), n_cols) \
+        if chunk is None else int(chunk)
+    parts = []
+    for t0 in range(0, n_cols, step):
+        yk = y if step >= n_cols else y[:, :, t0:t0 + step]
+        if step < n_cols:
+            yk = yk.contiguous() if on_device else np.ascontiguousarray(yk)
+        parts.append(run(yk))
+    return parts
+
+
+def _result(pb: _Problem, parts, own_attrs: dict, info_names, return_info: bool):
+    """The image (and with `return_info` the dataset) from the raw outputs of the passes."""
+    da, src, dim, coil_dim, spatial, cols, rest, names, on_device = (pb.da, pb.src, pb.dim, pb.coil_dim, pb.spatial, pb.cols,
+                                                                     pb.rest, pb.names, pb.on_device)
+
+    def joined(name, axis):
+        vals = [getattr(p, name) for p in parts]
+        if len(vals) == 1:
+            return vals[0]
+        if on_device:
+            import torch
+
+            return torch.cat(vals, dim=axis)
+        return np.concatenate(vals, axis=axis)
+
+    # the image: (x, y, z, columns) -> the input's order without the coil dim, the image dims in place of `dim`
+    img = joined("x", 1).reshape(tuple(spatial) + cols)
+    out_dims = []
+    for n in src.dims:
+        if n != coil_dim:
+            out_dims.extend(names if n == dim else (n,))
+    have = list(names) + rest
+    order = [have.index(n) for n in out_dims]
+    if order != list(range(len(have))):
+        img = img.permute(order).contiguous() if on_device else np.ascontiguousarray(np.transpose(img, order))
+    coords = {key: co for key, co in src.coords.items() if co.dim not in (dim, coil_dim)}
+    for a, n in enumerate(names):
+        coords[n] = Coordinate(n, (np.arange(spatial[a]) - spatial[a] // 2) * pb.fov[a] / spatial[a], {})
+    attrs = _attrs(src, names, pb.table, _label(pb.density))
+    attrs.update(own_attrs)
+    image = LabeledArray(img, out_dims, coords, attrs, src.name)
+    if not return_info:
+        return like_input(image, da)
+    from ..fitting.dataset import LabeledDataset
+
+    col_coords = {key: co for key, co in coords.items() if co.dim in rest}
+    info = {name: LabeledArray(joined(name, 0).reshape(cols), rest, col_coords) for name in info_names}
+    ds = LabeledDataset(dict(image=image, **info), _copy.copy(attrs))
+    return ds.to_xarray() if is_xarray(da) else ds
+
+
 def recon_cg_sense(da, trajectory, sensitivities, matrix=None, iterations: int = 20, tol: float = 1e-6,
                    regularization: float = 0.0, density=None, noise_cov=None, oversampling: float = 2.0, width: int = 4,
                    dim: str = DIMS.sample, coil_dim: str = DIMS.coil, out_dim=None, fov=1.0, readout_time=None,
@@ -110,110 +259,11 @@ def recon_cg_sense(da, trajectory, sensitivities, matrix=None, iterations: int =
         raise ValueError(f"iterations must be an integer >= 0, got {iterations!r}")
     tol = _number(tol, "tol")
     reg = _number(regularization, "regularization")
-    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1):
-        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
-    src0 = as_labeled(da)
-    _check_dims(src0, (dim, coil_dim), "recon_cg_sense")
-    if dim == coil_dim:
-        raise ValueError(f"coil_dim: {coil_dim!r} is the sample dim")
-    c = src0.sizes[coil_dim]
-    if not 1 <= c <= MAX_COILS:
-        raise ValueError(f"coil_dim: {c} coils along {coil_dim!r}, supported are 1 ... {MAX_COILS}")
-    k = _trajectory(trajectory)
-    d = k.shape[1]
-    if k.shape[0] != src0.sizes[dim]:
-        raise ValueError(f"trajectory: {k.shape[0]} samples for a {dim!r} dim of {src0.sizes[dim]} points")
-    sens, spatial = _sens(sensitivities, coil_dim, d, c)
-    if matrix is not None:
-        mat = _per_dim(matrix, d, "matrix", _int)
-        if mat is None or tuple(mat) != tuple(spatial):
-            raise ValueError(f"matrix: {matrix!r} disagrees with the sensitivities' spatial shape {tuple(spatial)}")
-    rest = [n for n in src0.dims if n not in (dim, coil_dim)]
-    names = _names(out_dim, d, X_DIMS, "out_dim", rest)
-    f = _fov(fov, d)
-    linv = None if noise_cov is None else _linv(noise_cov, c)
-    t = grid_table(k, spatial, oversampling, width, density)
-
-    da_t = _readout(da, readout_time, dim, False)
-    src = as_labeled(da_t)
-    y, _ = device_data(src)
-    on_device = hasattr(y, "detach")
-    perm = [src.get_axis_num(coil_dim), src.get_axis_num(dim)] + [src.get_axis_num(n) for n in rest]
-    if perm != list(range(src.ndim)):
-        y = y.permute(perm) if on_device else np.transpose(y, perm)
-    cols = tuple(int(n) for n in y.shape[2:])
-    n_samples, n_cols, n_vox = int(k.shape[0]), int(np.prod(cols, dtype=np.int64)), int(np.prod(spatial))
-    if n_cols < 1:
-        raise ValueError(f"da: an empty dimension among {tuple(rest)}")
-    y = y.reshape(c, n_samples, n_cols)
-    y = y.contiguous() if on_device else np.ascontiguousarray(y)
-
-    # the maps: complex128 on the device, [C, V]; whitening is one axis_dft along the coil axis of maps and data
-    if on_device:
-        import torch
-
-        s = (sens if hasattr(sens, "detach") else torch.from_numpy(np.array(sens, dtype=np.complex128, order="C")))
-        s = s.to(device=y.device, dtype=torch.complex128).reshape(c, n_vox).contiguous()
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.complex128)).to(y.device)  # noqa: E731
-    else:
-        s = np.array(sens, dtype=np.complex128, order="C").reshape(c, n_vox)
-        up = lambda a: np.ascontiguousarray(a, dtype=np.complex128)  # noqa: E731
-    if linv is not None:
-        white = up(linv)
-        s = dev.axis_dft(s, 0, white)
-        y = dev.axis_dft(y, 0, white)
-    energy = s.real ** 2 + s.imag ** 2
-    energy = energy.sum(dim=0).cpu().numpy() if on_device else energy.sum(axis=0)
-    lam = reg * normal_scale(energy, t.density, n_vox)
-
-    # the tables of both chains go up once; SparseTable keeps its own device copy
-    to_voxels, to_samples = [up(a) for a in _image_tables(t, 1.0)], [up(a) for a in _image_tables(t, -1.0)]
-
-    def adjoint(v):  # [C, S, T] -> [C, V, T]
-        g = dev.axis_sparse(v, 1, t.grid)
-        return _to_voxels(g, 1, t, to_voxels).reshape(c, n_vox, v.shape[2])
-
-    def forward(u):  # [C, V, T] -> [C, S, T]
-        return _to_samples(u.reshape((c,) + tuple(spatial) + (u.shape[2],)), 1, t, to_samples)
-
-    step = default_chunk(c, t.oversampled, y.dtype.itemsize if not on_device else y.element_size(), n_cols) if chunk is None \
-        else int(chunk)
-    parts = []
-    for t0 in range(0, n_cols, step):
-        yk = y if step >= n_cols else y[:, :, t0:t0 + step]
-        if step < n_cols:
-            yk = yk.contiguous() if on_device else np.ascontiguousarray(yk)
-        parts.append(dev.cg_sense(yk, s, adjoint, forward, lam, int(iterations), tol))
-
-    def joined(name, axis):
-        vals = [getattr(p, name) for p in parts]
-        if len(vals) == 1:
-            return vals[0]
-        return torch.cat(vals, dim=axis) if on_device else np.concatenate(vals, axis=axis)
-
-    # the image: (x, y, z, columns) -> the input's order without the coil dim, the image dims in place of `dim`
-    img = joined("x", 1).reshape(tuple(spatial) + cols)
-    out_dims = []
-    for n in src.dims:
-        if n != coil_dim:
-            out_dims.extend(names if n == dim else (n,))
-    have = list(names) + rest
-    order = [have.index(n) for n in out_dims]
-    if order != list(range(len(have))):
-        img = img.permute(order).contiguous() if on_device else np.ascontiguousarray(np.transpose(img, order))
-    coords = {key: co for key, co in src.coords.items() if co.dim not in (dim, coil_dim)}
-    for a, n in enumerate(names):
-        coords[n] = Coordinate(n, (np.arange(spatial[a]) - spatial[a] // 2) * f[a] / spatial[a], {})
-    attrs = _attrs(src, names, t, _label(density))
-    attrs[ATTRS.cgsense_iterations] = int(iterations)
-    attrs[ATTRS.cgsense_tol] = tol
-    attrs[ATTRS.cgsense_regularization] = reg
-    image = LabeledArray(img, out_dims, coords, attrs, src.name)
-    if not return_info:
-        return like_input(image, da)
-    from ..fitting.dataset import LabeledDataset
-
-    col_coords = {key: co for key, co in coords.items() if co.dim in rest}
-    info = {name: LabeledArray(joined(name, 0).reshape(cols), rest, col_coords) for name in ("residual", "iterations", "status")}
-    ds = LabeledDataset(dict(image=image, **info), _copy.copy(attrs))
-    return ds.to_xarray() if is_xarray(da) else ds
+    _columns(chunk)
+    pb = _problem("recon_cg_sense", da, trajectory, sensitivities, matrix, density, noise_cov, oversampling, width, dim,
+                  coil_dim, out_dim, fov, readout_time)
+    _upload(pb, readout_time)
+    lam = reg * normal_scale(pb.energy, pb.table.density, pb.n_vox)
+    parts = _passes(pb, chunk, lambda yk: dev.cg_sense(yk, pb.s, pb.adjoint, pb.forward, lam, int(iterations), tol))
+    own = {ATTRS.cgsense_iterations: int(iterations), ATTRS.cgsense_tol: tol, ATTRS.cgsense_regularization: reg}
+    return _result(pb, parts, own, ("residual", "iterations", "status"), return_info)
