@@ -634,6 +634,28 @@ int xm_species_separate(const void* x, void* y, const int64_t* dims, const int64
                         double* residual, int32_t* status, int fit, double max_field, double span, int dtype,
                         void* stream);
 
+/* ---- Lipid-subspace (L2) suppression of 1H MRSI (this backend's own definition, the reference
+ * has none).  A row is one FID of T samples, time stride 1, rows `x_row_stride` / `y_row_stride` elements apart.  With
+ * the orthonormal vectors u_k (k < rank) of the lipid subspace and the weights w_k, one launch of k_lipid_project writes
+ *   y[t] = x[t] - sum_k u_k[t] w_k c_k,   c_k = sum_t conj(u_k[t]) x[t],
+ * for every row, all arithmetic fp64, every sum in one defined order, the result rounded once to `dtype`.
+ * `tables` (device, fp64, 16-byte aligned): U[T][rank] as (re, im), then w[rank].  `apply`: a device byte per row, or
+ * NULL for every row; a row whose byte is 0 is copied bit for bit.  `status` (device, one int32 per row): 0 done, 1
+ * copied (apply 0), 2 a non-finite sample (the row's output is NaN; no other row is touched).  A row's output depends
+ * on its own samples and the tables only, bit for bit: not on the batch, its place in a tile of 16 rows, or the strides.
+ * x == y with equal strides is allowed (a workgroup writes only the rows it alone reads); any other overlap is refused.
+ * `dtype`: XM_C64 / XM_C128; on top of it XM_LIPID_FMA selects the plain-FMA form of both stages (default: the fp64
+ * matrix cores), XM_LIPID_SKIP_COEF / XM_LIPID_SKIP_APPLY leave a stage out (timing only).
+ * XM_ERR_INVALID_ARG before any HIP call, nothing written: T outside 2 ... 65536, rank outside 1 ... 64, n_rows < 0 or
+ * more than 2^31 - 1 tiles of 16 rows, a null x, y, tables or status, a row stride < T, tables not 16-byte aligned, x or
+ * y not aligned to an element, overlapping x and y, an unknown dtype.  n_rows == 0 (with T, rank and dtype in range) returns 0 without a launch,
+ * whatever the pointers hold. */
+#define XM_LIPID_FMA 0x100
+#define XM_LIPID_SKIP_COEF 0x200
+#define XM_LIPID_SKIP_APPLY 0x400
+int xm_lipid_project(const void* x, void* y, int64_t n_rows, int64_t x_row_stride, int64_t y_row_stride, int T, int rank,
+                     const double* tables, const uint8_t* apply, int32_t* status, int dtype, void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

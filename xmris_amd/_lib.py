@@ -47,6 +47,10 @@ XM_SPECIES_SKIP_COARSE = 0x200
 XM_SPECIES_SKIP_REFINE = 0x400
 XM_SPECIES_SKIP_APPLY = 0x800
 
+XM_LIPID_FMA = 0x100
+XM_LIPID_SKIP_COEF = 0x200
+XM_LIPID_SKIP_APPLY = 0x400
+
 XM_SENSE_WORKSPACE_BYTES = 256
 XM_CGS_VOXELS = 16
 XM_L1_MAX_BLOCK = 16
@@ -117,6 +121,7 @@ SIGNATURES = {
                              _p, _p, _p, _p, _p, _p]),
     "xm_species_separate": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _l, _l, _p, _l, _l, _p, _p, _p, _i, ctypes.c_double,
                                  ctypes.c_double, _i, _p]),
+    "xm_lipid_project": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _i, _p]),
     "xm_gather_row_c128":(_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

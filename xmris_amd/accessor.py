@@ -235,6 +235,15 @@ class XmrisMrsiMixin:
                                 readout_time=readout_time, sample_dim=sample_dim, field_map=field_map,
                                 fit_field=fit_field, max_field=max_field, share=share, return_field=return_field)
 
+    def remove_lipids(self, lipid_mask=None, *, basis=None, dims=None, level: float = 0.01, rank=None, apply_mask=None,
+                      return_basis: bool = False, dim: str = DIMS.time):
+        """Lipid-subspace (L2) suppression: every row minus its weighted projection onto the subspace of the scalp
+        voxels' FIDs, one launch (an addition of this backend)."""
+        from .processing.lipids import remove_lipids
+
+        return remove_lipids(self._obj, lipid_mask, basis=basis, dims=dims, level=level, rank=rank,
+                             apply_mask=apply_mask, return_basis=return_basis, dim=dim)
+
     def correct_readout_time(self, offsets, dim: str = DIMS.time, sample_dim: str = DIMS.sample, pad_to=None, dwell=None,
                              inverse: bool = False):
         """Undo the acquisition delay of each sample of a non-Cartesian readout."""

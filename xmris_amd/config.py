@@ -104,6 +104,10 @@ class _Attrs(_Vocabulary):
     species_nsa = XmrisTerm("species_nsa", "Effective number of signal averages of each species' estimate.")
     species_field = XmrisTerm("species_field", "Field offset of the separation model: 'none', 'given' or 'fitted'.")
     species_max_field = XmrisTerm("species_max_field", "Largest field offset the fit searched.", "Hz")
+    lipid_level = XmrisTerm("lipid_level", "Singular value, relative to the largest, at which the lipid removal halves a component.")
+    lipid_rank = XmrisTerm("lipid_rank", "Components of the lipid subspace that were removed.")
+    lipid_beta = XmrisTerm("lipid_beta", "Weight of the L2 lipid penalty, 1 / (lipid_level x largest singular value)^2.")
+    lipid_rows = XmrisTerm("lipid_rows", "Number of lipid rows (scalp voxels or given basis rows) the subspace was made from.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 

@@ -1674,6 +1674,137 @@ def species_separate(x, echo_axis: int, col_axes, echo_times, frequencies, decay
                          levels=(sum(n > 1 for n, _ in rl), sum(n > 1 for n, _ in cl)))
 
 
+class LipidResult:
+    """Raw outputs of ``lipid_project``: `out` like x, `status` int32 per row (0 done, 1 copied, 2 non-finite sample:
+    NaN); `copied`: whether the layout needed the one contiguous copy."""
+
+    __slots__ = ("out", "status", "copied")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+LIPID_MAX_RANK = 64
+LIPID_MIN_POINTS = 2
+LIPID_MAX_POINTS = 65536
+LIPID_FLAGS = {"fma": _lib.XM_LIPID_FMA, "coef": _lib.XM_LIPID_SKIP_COEF, "apply": _lib.XM_LIPID_SKIP_APPLY}
+
+
+def lipid_rows(x, axes, mask):
+    """The rows of the device tensor `x` ([..., time]) whose position along the leading `axes` lies inside the boolean
+    host array `mask` (shape: the sizes of `axes`), as one [n, time] complex128 tensor; every other leading axis
+    contributes rows."""
+    torch = _torch()
+    _require_device(x)
+    lead = list(range(x.dim() - 1))
+    axes = [a % x.dim() for a in axes]
+    perm = axes + [a for a in lead if a not in axes] + [x.dim() - 1]
+    m = torch.from_numpy(np.array(mask, dtype=np.bool_)).to(x.device)  # (a copy: the caller's mask may be read-only)
+    return x.permute(perm)[m].reshape(-1, x.shape[-1]).to(torch.complex128)
+
+
+def lipid_subspace(L, kmax: int = LIPID_MAX_RANK):
+    """Singular values (all min(n, T), descending, ties to the lower index) and the first `kmax` left vectors u_k (host
+    complex128 [T, k]) of M = L^T, L the [n, T] complex device tensor of lipid FIDs.  The Gram matrix, whichever of
+    M M^H (T x T) and M^H M (n x n) is smaller, is one complex128 matmul on the device; its Hermitian eigen-decomposition
+    is host numpy; with the n x n form u_k = M v_k / sigma_k is a second matmul on the device (a component with
+    sigma_k = 0 has u_k = 0).  A non-finite Gram matrix raises ValueError."""
+    torch = _torch()
+    _require_device(L)
+    L = L.to(torch.complex128)
+    n, T = L.shape
+    small_t = T <= n
+    G = (L.transpose(0, 1) @ L.conj()) if small_t else (L.conj() @ L.transpose(0, 1))
+    g = G.cpu().numpy()
+    if not np.all(np.isfinite(g.view(np.float64))):
+        raise ValueError("the lipid basis has a non-finite sample (or its Gram matrix overflows)")
+    ev, vec = np.linalg.eigh(0.5 * (g + g.conj().T))
+    order = np.argsort(-ev, kind="stable")
+    sigma = np.sqrt(np.maximum(ev[order], 0.0))
+    k = min(int(kmax), len(sigma))
+    v = np.ascontiguousarray(vec[:, order[:k]])
+    if small_t:
+        return sigma, v
+    inv = np.where(sigma[:k] > 0, 1.0 / np.where(sigma[:k] > 0, sigma[:k], 1.0), 0.0)
+    u = (L.transpose(0, 1) @ torch.from_numpy(v * inv[None, :]).to(L.device)).cpu().numpy()
+    return sigma, np.ascontiguousarray(u)
+
+
+def lipid_tables(U, w, device=None):
+    """The fp64 table of xm_lipid_project, U[T][r] as (re, im) then w[r]: a host array, or with `device` the tensor there."""
+    U = np.asarray(U, dtype=np.complex128)
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if U.ndim != 2 or U.shape[1] != len(w):
+        raise ValueError(f"lipid_tables: U must be [T, r] with one weight per column, got {U.shape} and {len(w)} weights")
+    tab = np.concatenate([np.stack([U.real, U.imag], axis=-1).reshape(-1), w])
+    return tab if device is None else _torch().from_numpy(np.ascontiguousarray(tab)).to(device)
+
+
+def lipid_project(x, basis_record, apply=None, out=None, form=None, _skip=()) -> LipidResult:
+    """out = x - U diag(w) U^H x along the last axis of the complex64 / complex128 device tensor `x` in one launch of
+    k_lipid_project (xm_lipid_project).  `basis_record`: anything with ``rank``, ``n_time`` and
+    ``table_on(device)`` (a ``LipidBasis``).  `apply`: None, or a boolean array / tensor of x's leading shape; rows
+    where it is false are copied bit for bit.  `out`: None (a fresh tensor), or a tensor of x's shape, dtype and layout
+    class; ``out is x`` works in place.  The tensor is addressed where it lies when its time stride is 1 and the
+    leading axes collapse into one strided row level; any other layout costs one contiguous copy (`copied`).
+    `form`: None / "mfma" (the fp64 matrix cores) or "fma"; `_skip` (timing only): of "coef", "apply"."""
+    torch = _torch()
+    _require_device(x)
+    code = _dtype_code(x)
+    if x.dim() < 1:
+        raise ValueError("lipid_project needs at least the time axis")
+    T, r = int(x.shape[-1]), int(basis_record.rank)
+    if T != int(basis_record.n_time):
+        raise ValueError(f"lipid_project: the data has {T} points along time, the basis {basis_record.n_time}")
+    if form not in (None, "mfma", "fma"):
+        raise ValueError(f"form must be 'mfma' or 'fma', got {form!r}")
+    lead = tuple(x.shape[:-1])
+    n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    tables = basis_record.table_on(x.device)
+
+    def row_level(t_):
+        if t_.shape[-1] > 1 and t_.stride(-1) != 1:
+            return None
+        lv = _collapse(lead, [[t_.stride(a)] for a in range(len(lead))])
+        if len(lv) > 1 or (lv and lv[0][1][0] < T):
+            return None
+        return lv[0][1][0] if lv else T
+
+    in_place = out is x
+    if out is not None and (tuple(out.shape) != tuple(x.shape) or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError("out must have x's shape, dtype and device")
+    xs, copied = x, False
+    sx = row_level(xs)
+    if sx is None:
+        xs, copied, in_place = x.contiguous(), True, False
+        sx = T
+    if in_place:
+        ys = xs
+    elif out is not None and not copied and row_level(out) is not None:
+        ys = out
+    else:
+        ys = torch.empty(xs.shape, dtype=x.dtype, device=x.device)
+    sy = row_level(ys)
+    status = torch.empty(lead, dtype=torch.int32, device=x.device)
+    ap = None
+    if apply is not None:
+        ap = apply if isinstance(apply, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(apply))
+        if tuple(ap.shape) != lead:
+            raise ValueError(f"apply must have the data's leading shape {lead}, got {tuple(ap.shape)}")
+        ap = (ap != 0).to(device=x.device, dtype=torch.uint8).contiguous()
+    if form == "fma":
+        code |= LIPID_FLAGS["fma"]
+    for s in _skip:
+        code |= LIPID_FLAGS[s]
+    _lib.call("xm_lipid_project", xs.data_ptr(), ys.data_ptr(), n_rows, int(sx), int(sy), T, r, tables.data_ptr(),
+              ap.data_ptr() if ap is not None else None, status.data_ptr(), code, _stream(x))
+    if out is not None and ys is not out:
+        out.copy_(ys)
+        ys = out
+    return LipidResult(out=ys, status=status, copied=copied)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 

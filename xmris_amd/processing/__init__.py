@@ -8,6 +8,7 @@ from .fid import apodize_exp, apodize_lg, to_fid, to_spectrum, zero_fill
 from .grappa import GrappaWeights, grappa_calibrate, grappa_fill
 from .cgsense import recon_cg_sense
 from .l1sense import recon_l1_sense
+from .lipids import LipidBasis, lipid_basis, remove_lipids
 from .grid import degrid_kspace, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward
 from .mrsi import to_image, to_kspace
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
@@ -21,7 +22,7 @@ __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense",
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense", "recon_l1_sense",
            "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
-           "separate_species", "simulate_echoes", "species_matrix"]
+           "separate_species", "simulate_echoes", "species_matrix", "LipidBasis", "lipid_basis", "remove_lipids"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled
