@@ -656,6 +656,31 @@ int xm_species_separate(const void* x, void* y, const int64_t* dims, const int64
 int xm_lipid_project(const void* x, void* y, int64_t n_rows, int64_t x_row_stride, int64_t y_row_stride, int T, int rank,
                      const double* tables, const uint8_t* apply, int32_t* status, int dtype, void* stream);
 
+/* ---- Temporal-subspace SENSE (this backend's own definition, the reference has none).  With the
+ * basis V [rank, n_time] complex128 (rows need not be orthonormal), rank <= XM_SUB_MAX_RANK, three kernels around the
+ * xm_cgs_* iteration and the NUFFT chains:
+ *   xm_sub_project  b[c, s, r, f] = sum_t m[s, t] conj(V[r, t]) y[c, s, f, t]    (k_sub_project: the one pass over y)
+ *   xm_sub_mix      z[c, s, r, f] = sum_r' K[s, r, r'] a[c, s, r', f]            (k_sub_mix; z == a is allowed)
+ *   xm_sub_expand   x[v, f, t]    = sum_r U[v, r, f] V[r, t]                      (k_sub_expand; x complex128)
+ * y is addressed where it lies: element (c, s, f, t) at y + c coil_stride + s sample_stride + f frame_stride + t (in
+ * elements; the time stride is 1).  b, a, z: [C, S, rank, F] contiguous in `dtype`; `sampling`: a device byte per
+ * (s, t), [S, T] contiguous, or NULL for all ones -- a position whose byte is 0 is selected out, whatever y holds there
+ * (NaN included) reaches no output.  K: [S, rank, rank] complex128; U: [V, rank, F] complex128.  All arithmetic fp64 in
+ * spelt-out FMAs, every sum one chain in ascending t / r' / r from zero, rounded once to the output dtype; no atomics.
+ * An output depends on its own inputs only, bit for bit: not on the batch, its place in a tile, F or the strides.
+ * XM_ERR_INVALID_ARG before any HIP call, nothing written: an unknown dtype, rank outside 1 ... 32 or (project, expand)
+ * above n_time, a size outside 1 ... 2^31 - 1, more than 2^50 elements (for y: reached through the strides), a null y, b,
+ * basis, a, z, kernel, u or x, a negative stride, a pointer not aligned to its element (the complex128 tables: 16
+ * bytes), an output that overlaps an input (other than z == a). */
+#define XM_SUB_MAX_RANK 32
+int xm_sub_project(const void* y, void* b, const void* basis, const uint8_t* sampling, int64_t n_coils, int64_t n_samples,
+                   int64_t n_frames, int64_t n_time, int rank, int64_t coil_stride, int64_t sample_stride,
+                   int64_t frame_stride, int dtype, void* stream);
+int xm_sub_mix(const void* a, void* z, const void* kernel, int64_t n_coils, int64_t n_samples, int64_t n_frames, int rank,
+               int dtype, void* stream);
+int xm_sub_expand(const void* u, const void* basis, void* x, int64_t n_vox, int64_t n_frames, int64_t n_time, int rank,
+                  void* stream);
+
 /* ---- A7  host-side autophase search (no GPU involved; O(1) per dataset) ------------------------
  * Objectives of processing/phasing.py:100-157 and the differential-evolution driver the reference
  * reaches through scipy (phasing.py:276-284: best1bin, tol, seed, bounds p0 in [-180,180] deg,

@@ -17,7 +17,8 @@ from .vendor.bruker import remove_digital_filter
 from .processing import (align_averages, baseline_als, combine_coils, degrid_kspace, denoise_mppca, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward, recon_cg_sense, recon_l1_sense, apodize_exp, apodize_lg, autophase, autophase_each, fft, fftc, fftshift, ifft, ifftc, ifftshift, phase,
                          remove_water, sense_maps, to_fid, to_image, to_kspace, to_spectrum, unfold_sense, zero_fill,
                          correct_readout_time, readout_offsets, shift_time, GrappaWeights, grappa_calibrate, grappa_fill, espirit_maps,
-                         separate_species, simulate_echoes, species_matrix, LipidBasis, lipid_basis, remove_lipids)
+                         separate_species, simulate_echoes, species_matrix, LipidBasis, lipid_basis, remove_lipids,
+                         TemporalBasis, recon_subspace, temporal_basis)
 
 DataArray = LabeledArray  # convenience alias for code written against xarray's constructor signature
 register_xarray_accessor()  # no-op when xarray is absent or the name `xmr` is already owned
@@ -28,4 +29,5 @@ __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense", "recon_l1_sense",
            "shift_time", "correct_readout_time", "readout_offsets", "fit_kinetics", "simulate_kinetics",
            "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
-           "separate_species", "simulate_echoes", "species_matrix", "LipidBasis", "lipid_basis", "remove_lipids"]
+           "separate_species", "simulate_echoes", "species_matrix", "LipidBasis", "lipid_basis", "remove_lipids",
+           "TemporalBasis", "recon_subspace", "temporal_basis"]

@@ -54,6 +54,7 @@ XM_LIPID_SKIP_APPLY = 0x400
 XM_SENSE_WORKSPACE_BYTES = 256
 XM_CGS_VOXELS = 16
 XM_L1_MAX_BLOCK = 16
+XM_SUB_MAX_RANK = 32
 
 XM_ERR_INVALID_ARG = -1
 XM_ERR_UNSUPPORTED_N = -2
@@ -122,6 +123,9 @@ SIGNATURES = {
     "xm_species_separate": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _l, _l, _p, _l, _l, _p, _p, _p, _i, ctypes.c_double,
                                  ctypes.c_double, _i, _p]),
     "xm_lipid_project": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _i, _p]),
+    "xm_sub_project": (_i, [_p, _p, _p, _p, _l, _l, _l, _l, _i, _l, _l, _l, _i, _p]),
+    "xm_sub_mix": (_i, [_p, _p, _p, _l, _l, _l, _i, _i, _p]),
+    "xm_sub_expand": (_i, [_p, _p, _p, _l, _l, _l, _i, _p]),
     "xm_gather_row_c128":(_i, [_p, _l, _i, _p, _i, _p, _i, _p]),
     "xm_pipeline_fused": (_i, [_p, _l, _p, _p, _p, _l, _i, _i, _i, _u, _p, _p, _i, _p]),
     "xm_pipeline_fused_ramp": (_i, [_p, _l, _p, _p, ctypes.c_double, ctypes.c_double, _l, _i, _i, _i, _u, _p, _p, _i, _p]),

@@ -206,6 +206,21 @@ class XmrisMrsiMixin:
                               coil_dim=coil_dim, out_dim=out_dim, fov=fov, readout_time=readout_time, chunk=chunk,
                               return_info=return_info)
 
+    def recon_subspace(self, trajectory, sensitivities, basis, sampling=None, matrix=None, iterations: int = 30,
+                       tol: float = 1e-6, regularization: float = 0.0, density=None, noise_cov=None, oversampling: float = 2.0,
+                       width: int = 4, dim: str = DIMS.sample, coil_dim: str = DIMS.coil, time_dim: str = DIMS.time,
+                       out_dim=None, fov=1.0, chunk=None, return_info: bool = False, return_coefficients: bool = False):
+        """Temporal-subspace iterative SENSE of (k, t)-undersampled non-Cartesian samples: only the coefficient columns
+        of a basis from ``temporal_basis`` go through the NUFFT chains (an addition of this backend; DESIGN.md section
+        26)."""
+        from .processing.subspace import recon_subspace
+
+        return recon_subspace(self._obj, trajectory, sensitivities, basis, sampling=sampling, matrix=matrix,
+                              iterations=iterations, tol=tol, regularization=regularization, density=density,
+                              noise_cov=noise_cov, oversampling=oversampling, width=width, dim=dim, coil_dim=coil_dim,
+                              time_dim=time_dim, out_dim=out_dim, fov=fov, chunk=chunk, return_info=return_info,
+                              return_coefficients=return_coefficients)
+
     def espirit_maps(self, matrix, kernel=None, dims=(DIMS.kx, DIMS.ky), coil_dim: str = DIMS.coil,
                      time_dim: str = DIMS.time, acs_points: int = 8, threshold: float = 0.02, crop: float = 0.8,
                      n_maps: int = 1, noise_cov=None, phase_ref: int = 0, return_eigenvalues: bool = False):

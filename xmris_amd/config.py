@@ -108,6 +108,8 @@ class _Attrs(_Vocabulary):
     lipid_rank = XmrisTerm("lipid_rank", "Components of the lipid subspace that were removed.")
     lipid_beta = XmrisTerm("lipid_beta", "Weight of the L2 lipid penalty, 1 / (lipid_level x largest singular value)^2.")
     lipid_rows = XmrisTerm("lipid_rows", "Number of lipid rows (scalp voxels or given basis rows) the subspace was made from.")
+    subspace_rank = XmrisTerm("subspace_rank", "Rank of the temporal subspace of the reconstruction.")
+    subspace_sampled_fraction = XmrisTerm("subspace_sampled_fraction", "Fraction of the (sample, time) positions that were acquired.")
     denoise_rank = XmrisTerm("denoise_rank", "Components kept by the patch PCA denoising: 'mp' (Marchenko-Pastur rule) or the number.")
 
 
@@ -120,6 +122,7 @@ class _Dims(_Vocabulary):
     coil = XmrisTerm("coil", "Receive coils.")
     echo = XmrisTerm("echo", "Echoes.")
     species = XmrisTerm("species", "Chemical species separated from the echoes.")
+    coefficient = XmrisTerm("coefficient", "Coefficients of a temporal-subspace basis.")
     sample = XmrisTerm("sample", "Samples of a non-Cartesian k-space trajectory.")
     kx = XmrisTerm("kx", "k-space axis x.")
     ky = XmrisTerm("ky", "k-space axis y.")

@@ -1805,6 +1805,159 @@ def lipid_project(x, basis_record, apply=None, out=None, form=None, _skip=()) ->
     return LipidResult(out=ys, status=status, copied=copied)
 
 
+SUB_MAX_RANK = _lib.XM_SUB_MAX_RANK
+
+
+def _sub_basis(basis, what: str = "basis"):
+    torch = _torch()
+    _require_device(basis)
+    if basis.dtype != torch.complex128 or basis.dim() != 2 or not basis.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous complex128 tensor [R, T], got {tuple(basis.shape)} of {basis.dtype}")
+    r, t = (int(n) for n in basis.shape)
+    if not 1 <= r <= SUB_MAX_RANK or r > t:
+        raise ValueError(f"{what}: rank {r} must be in 1 ... {SUB_MAX_RANK} and at most T = {t}")
+    return r, t
+
+
+def sub_project(y, basis, sampling=None):
+    """One launch of k_sub_project (xm_sub_project): ``b[c, s, r, f] = sum_t m[s, t] conj(V[r, t])
+    y[c, s, f, t]`` in y's dtype, [C, S, R, F].  y: a complex64 / complex128 device tensor [C, S, F, T] whose time
+    stride is 1 (any coil, sample and frame strides: it is addressed where it lies; another time stride costs one
+    contiguous copy); basis: V [R, T] complex128; sampling: None (all ones) or a contiguous uint8 / bool tensor [S, T] --
+    what y holds where it is 0 reaches no output."""
+    torch = _torch()
+    _require_device(y)
+    code = _dtype_code(y)
+    if y.dim() != 4:
+        raise ValueError(f"y must be [C, S, F, T], got {tuple(y.shape)}")
+    c, s, f, t = (int(n) for n in y.shape)
+    r, tb = _sub_basis(basis)
+    if tb != t:
+        raise ValueError(f"sub_project: the data has {t} points along time, the basis {tb}")
+    if t > 1 and y.stride(3) != 1:
+        y = y.contiguous()
+    m = None
+    if sampling is not None:
+        _require_device(sampling)
+        if sampling.dtype not in (torch.uint8, torch.bool) or tuple(sampling.shape) != (s, t) or not sampling.is_contiguous():
+            raise ValueError(f"sampling must be a contiguous uint8 / bool tensor of shape {(s, t)}")
+        m = sampling
+    b = torch.empty((c, s, r, f), dtype=y.dtype, device=y.device)
+    if b.numel():
+        _lib.call("xm_sub_project", y.data_ptr(), b.data_ptr(), basis.data_ptr(), None if m is None else m.data_ptr(), c, s, f, t,
+                  r, int(y.stride(0)), int(y.stride(1)), int(y.stride(2)), code, _stream(y))
+    return b
+
+
+def sub_mix(a, kernel, out=None):
+    """One launch of k_sub_mix (xm_sub_mix): ``z[c, s, r, f] = sum_r' K[s, r, r'] a[c, s, r', f]``.  a: contiguous
+    complex64 / complex128 [C, S, R, F]; kernel: K [S, R, R] complex128; `out`: None (a fresh tensor), or a tensor like
+    a -- ``out is a`` works in place and gives the same bits."""
+    torch = _torch()
+    _require_device(a)
+    code = _dtype_code(a)
+    if a.dim() != 4 or not a.is_contiguous():
+        raise ValueError(f"a must be a contiguous tensor [C, S, R, F], got {tuple(a.shape)}")
+    c, s, r, f = (int(n) for n in a.shape)
+    _cgs_c128(kernel, (s, r, r), "kernel")
+    z = torch.empty_like(a) if out is None else out
+    if z is not a and (tuple(z.shape) != tuple(a.shape) or z.dtype != a.dtype or not z.is_contiguous() or z.device != a.device):
+        raise ValueError("out must be contiguous with a's shape, dtype and device")
+    if a.numel():
+        _lib.call("xm_sub_mix", a.data_ptr(), z.data_ptr(), kernel.data_ptr(), c, s, f, r, code, _stream(a))
+    return z
+
+
+def sub_expand(u, basis):
+    """One launch of k_sub_expand (xm_sub_expand): ``x[v, f, t] = sum_r U[v, r, f] V[r, t]``, complex128 [V, F, T].
+    u: contiguous complex128 [V, R, F]; basis: V [R, T] complex128."""
+    torch = _torch()
+    r, t = _sub_basis(basis)
+    if u.dim() != 3 or int(u.shape[1]) != r:
+        raise ValueError(f"u must be [V, {r}, F], got {tuple(u.shape)}")
+    v, _, f = (int(n) for n in u.shape)
+    _cgs_c128(u, (v, r, f), "u")
+    x = torch.empty((v, f, t), dtype=torch.complex128, device=u.device)
+    if x.numel():
+        _lib.call("xm_sub_expand", u.data_ptr(), basis.data_ptr(), x.data_ptr(), v, f, t, r, _stream(u))
+    return x
+
+
+class SubspaceSetup:
+    """What ``subspace_sense`` needs besides the data, made once per call by ``subspace_setup``: `basis` V [R, T]
+    complex128 and `sampling` (uint8 [S, T], or None) on the device, `kernel` K [S, R, R] complex128 there, and the host
+    numbers `kappa` (sum_s w_s tr K_s / (R sum_s w_s)) and `fraction` (the mean of the flags)."""
+
+    __slots__ = ("basis", "sampling", "kernel", "kappa", "fraction")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def subspace_setup(basis, sampling, weights, n_samples: int, device) -> SubspaceSetup:
+    """K_s[r, r'] = sum_t m[s, t] conj(V[r, t]) V[r', t] as one complex128 matmul on `device` ([S, T] x [T, R^2]) and
+    kappa, read back once.  basis: host complex128 [R, T] or a device tensor; sampling: None or a host bool [S, T];
+    weights: the S density weights (host)."""
+    torch = _torch()
+    V = basis if hasattr(basis, "detach") else torch.from_numpy(np.ascontiguousarray(basis, dtype=np.complex128))
+    V = V.to(device=device, dtype=torch.complex128).contiguous()
+    r, t = (int(n) for n in V.shape)
+    if not 1 <= r <= SUB_MAX_RANK or r > t:
+        raise ValueError(f"basis: rank {r} must be in 1 ... {SUB_MAX_RANK} and at most T = {t}")
+    pairs = (V.conj()[:, None, :] * V[None, :, :]).reshape(r * r, t)  # [(r, r'), t]
+    if sampling is None:
+        m, fraction = None, 1.0
+        K = pairs.sum(dim=1).reshape(1, r, r).expand(int(n_samples), r, r).contiguous()
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(sampling, dtype=np.uint8)).to(device)
+        K = (m.to(torch.complex128) @ pairs.transpose(0, 1)).reshape(int(n_samples), r, r).contiguous()
+        fraction = float(m.to(torch.float64).mean().item())
+    w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(device)
+    trace = torch.diagonal(K, dim1=1, dim2=2).real.sum(dim=1)
+    kappa = float(((w * trace).sum() / (r * w.sum())).item())
+    return SubspaceSetup(basis=V, sampling=m, kernel=K, kappa=kappa, fraction=fraction)
+
+
+class SubspaceSense:
+    """Raw outputs of ``subspace_sense``: x [V, F, T] complex128, coefficients [V, R, F] complex128, and per frame
+    residual, iterations, status as ``CgSense``."""
+
+    __slots__ = ("x", "coefficients", "residual", "iterations", "status")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def subspace_sense(y, s, adjoint, forward, setup: SubspaceSetup, lam: float, iterations: int, tol: float) -> SubspaceSense:
+    """Temporal-subspace SENSE of the frames of y [C, S, F, T]: k_sub_project, then ``cg_sense``
+    unchanged on the folded system -- the state is [V R, F], the maps are repeated R times along the voxel axis, the two
+    chains run on R F columns and `forward` ends with k_sub_mix in place -- then k_sub_expand.  s, adjoint, forward as in
+    ``cg_sense``; `lam` is the final Tikhonov weight (kappa included).  Nothing is read back."""
+    c, n_s, f, _ = (int(n) for n in y.shape)
+    v = int(s.shape[1])
+    V, K = setup.basis, setup.kernel
+    r = int(V.shape[0])
+    b = sub_project(y, V, setup.sampling)  # [C, S, R, F]
+    s_rep = s.repeat_interleave(r, dim=1) if hasattr(s, "repeat_interleave") else np.repeat(s, r, axis=1)  # [C, V R]
+
+    def adj(a):  # [C, S R, F] -> [C, V R, F]
+        n = int(a.shape[2])
+        return adjoint(a.reshape(c, n_s, r * n)).reshape(c, v * r, n)
+
+    def fwd(u):  # [C, V R, F] -> [C, S R, F], mixed
+        n = int(u.shape[2])
+        z = forward(u.reshape(c, v, r * n)).reshape(c, n_s, r, n)
+        z = z.contiguous() if hasattr(z, "contiguous") else np.ascontiguousarray(z)
+        return sub_mix(z, K, out=z).reshape(c, n_s * r, n)
+
+    res = cg_sense(b.reshape(c, n_s * r, f), s_rep, adj, fwd, lam, iterations, tol)
+    coef = res.x.reshape(v, r, f)
+    return SubspaceSense(x=sub_expand(coef, V), coefficients=coef, residual=res.residual, iterations=res.iterations,
+                         status=res.status)
+
+
 def absmax_argmax(x):
     """phasing.py:229 ``int(np.argmax(np.abs(values)))``: (max |x|, first flat C-order index).
 

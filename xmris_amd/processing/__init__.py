@@ -9,6 +9,7 @@ from .grappa import GrappaWeights, grappa_calibrate, grappa_fill
 from .cgsense import recon_cg_sense
 from .l1sense import recon_l1_sense
 from .lipids import LipidBasis, lipid_basis, remove_lipids
+from .subspace import TemporalBasis, recon_subspace, temporal_basis
 from .grid import degrid_kspace, density_weights, grid_kspace, grid_table, nufft_adjoint, nufft_forward
 from .mrsi import to_image, to_kspace
 from .fourier import fft, fftc, fftshift, ifft, ifftc, ifftshift
@@ -22,7 +23,8 @@ __all__ = ["align_averages", "baseline_als", "combine_coils", "denoise_mppca", "
            "ifftc", "ifftshift", "autophase", "autophase_each", "phase", "remove_water", "to_image", "to_kspace", "sense_maps", "unfold_sense",
            "grid_kspace", "degrid_kspace", "nufft_adjoint", "nufft_forward", "density_weights", "grid_table", "recon_cg_sense", "recon_l1_sense",
            "shift_time", "correct_readout_time", "readout_offsets", "GrappaWeights", "grappa_calibrate", "grappa_fill", "espirit_maps",
-           "separate_species", "simulate_echoes", "species_matrix", "LipidBasis", "lipid_basis", "remove_lipids"]
+           "separate_species", "simulate_echoes", "species_matrix", "LipidBasis", "lipid_basis", "remove_lipids",
+           "TemporalBasis", "recon_subspace", "temporal_basis"]
 
 # the lazy chain's end computes itself in one fused launch where it can (labeled.LabeledArray.data)
 from .. import labeled as _labeled

@@ -130,9 +130,11 @@ def _problem(who: str, da, trajectory, sensitivities, matrix, density, noise_cov
     return pb
 
 
-def _upload(pb: _Problem, readout_time) -> _Problem:
+def _upload(pb: _Problem, readout_time, arrange=None) -> _Problem:
     """The second half of the set-up, which reaches the library: the data in the order (coil, sample, columns), the maps
-    and the tables on the device, the whitening."""
+    and the tables on the device, the whitening.  `arrange` (``recon_subspace``): takes the data as (coil, sample, *rest)
+    and returns it as the caller's kernels want it, with the column count and the sizes `_result` reshapes to, in place
+    of the contiguous [C, S, columns]."""
     da, dim, coil_dim, c, spatial, rest, t, sens, linv = (pb.da, pb.dim, pb.coil_dim, pb.c, pb.spatial, pb.rest, pb.table,
                                                           pb.sens, pb.linv)
     da_t = _readout(da, readout_time, dim, False)
@@ -146,8 +148,11 @@ def _upload(pb: _Problem, readout_time) -> _Problem:
     n_samples, n_cols, n_vox = int(len(t.density)), int(np.prod(cols, dtype=np.int64)), int(np.prod(spatial))
     if n_cols < 1:
         raise ValueError(f"da: an empty dimension among {tuple(rest)}")
-    y = y.reshape(c, n_samples, n_cols)
-    y = y.contiguous() if on_device else np.ascontiguousarray(y)
+    if arrange is None:
+        y = y.reshape(c, n_samples, n_cols)
+        y = y.contiguous() if on_device else np.ascontiguousarray(y)
+    else:
+        y, n_cols = arrange(y, on_device)
 
     # the maps: complex128 on the device, [C, V]; whitening is one axis_dft along the coil axis of maps and data
     if on_device:
@@ -195,8 +200,9 @@ def _passes(pb: _Problem, chunk, run):
     return parts
 
 
-def _result(pb: _Problem, parts, own_attrs: dict, info_names, return_info: bool):
-    """The image (and with `return_info` the dataset) from the raw outputs of the passes."""
+def _result(pb: _Problem, parts, own_attrs: dict, info_names, return_info: bool, info_dims=None, extra=None):
+    """The image (and with `return_info` the dataset) from the raw outputs of the passes.  `info_dims`: the dims of the
+    per-column outputs where they are not all of `rest`; `extra(joined, coords)`: further variables of the dataset."""
     da, src, dim, coil_dim, spatial, cols, rest, names, on_device = (pb.da, pb.src, pb.dim, pb.coil_dim, pb.spatial, pb.cols,
                                                                      pb.rest, pb.names, pb.on_device)
 
@@ -230,8 +236,12 @@ def _result(pb: _Problem, parts, own_attrs: dict, info_names, return_info: bool)
         return like_input(image, da)
     from ..fitting.dataset import LabeledDataset
 
+    if info_dims is not None:
+        rest, cols = list(info_dims), tuple(src.sizes[n] for n in info_dims)
     col_coords = {key: co for key, co in coords.items() if co.dim in rest}
     info = {name: LabeledArray(joined(name, 0).reshape(cols), rest, col_coords) for name in info_names}
+    if extra is not None:
+        info.update(extra(joined, coords))
     ds = LabeledDataset(dict(image=image, **info), _copy.copy(attrs))
     return ds.to_xarray() if is_xarray(da) else ds
 
