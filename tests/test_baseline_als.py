@@ -1,8 +1,12 @@
 """baseline_als (reference processing/baseline.py).  CPU: the oracle against the
 notebook's known-answer cell (pipeline/baseline.md:143-167).  GPU: the fp64 band-LDL' kernel vs the oracle's
-scipy.sparse spsolve (tolerance 1e-6 of the spectrum scale: the system's condition number is ~1e9)."""
+scipy.sparse spsolve (tolerance 1e-6 of the spectrum scale: the system's condition number is ~1e9).  The long-double
+reference of tests/_als_oracle.py, which tests/test_gpu_baseline_als.py holds the kernel to, is tied to that oracle here,
+and its cases are checked to be usable (profiles/als/tolerance.txt has the figures)."""
 import numpy as np
 import pytest
+
+import _als_oracle as als
 
 
 def _spectrum(n=1024, sw=2000.0, seed=1, nv=1):
@@ -32,6 +36,49 @@ def test_oracle_kat(oracle):
     assert spec.real[i] > 0.5 and abs(cor.values[i]) < 0.2 * abs(spec.real[i])
     with pytest.raises(ValueError, match="baseline_als"):
         oracle.baseline_als(da, dim="time")
+
+
+@pytest.fixture(scope="module")
+def als_figures(oracle):
+    """{(case, single): (e64, scipy, margin)} relative to max |y| of the row, as tests/tool_als_tolerance.py prints them:
+    the float64 recurrence and the scipy oracle against long double (the largest row), the weight margin (the smallest)."""
+    return {(case, single): als.figures(case, single, oracle.als_core) for case in als.CASES for single in (False, True)}
+
+
+def test_case_table_covers_the_tile_and_block_edges():
+    assert {c[0] for c in als.CASES} == {4, 5, 6, 31, 32, 33, 37, 1000}
+    assert {c[1] for c in als.CASES} >= {1, 31, 32, 33, 63, 64, 65, 131}
+    assert {(33, 33), (37, 65), (4, 131)} <= {c[:2] for c in als.CASES}
+    assert {c[2] for c in als.CASES} == set(als.PARAMS)
+
+
+@pytest.mark.parametrize("single", [False, True], ids=["float64", "float32"])
+@pytest.mark.parametrize("case", als.CASES, ids=als.case_id)
+def test_scipy_oracle_agrees_with_long_double(als_figures, case, single):
+    """The reference project's arithmetic (scipy's spsolve) lies within 4 x the float64 rounding error of the recurrence
+    from the long-double reference, case by case."""
+    e64, scipy_gap, _ = als_figures[case, single]
+    assert scipy_gap <= 4 * e64, (scipy_gap, e64)
+
+
+@pytest.mark.parametrize("single", [False, True], ids=["float64", "float32"])
+@pytest.mark.parametrize("case", als.CASES, ids=als.case_id)
+def test_weight_margin_of_every_case(als_figures, case, single):
+    """No point of any row comes within 64 x the GPU bound of its baseline at any iteration: no weight can flip."""
+    assert als_figures[case, single][2] >= 64 * als.bound(case)
+
+
+def test_bounds_are_16_e64(als_figures):
+    """The table of _als_oracle.BOUND is 16 x the largest e64 of each (lam, p), rounded up by less than 10 %."""
+    for key, b in als.BOUND.items():
+        worst = max(f[0] for (case, _), f in als_figures.items() if case[2][:2] == key)
+        assert 16 * worst <= b <= 1.1 * 16 * worst, (key, worst, b)
+
+
+def test_reference_keeps_a_converged_row():
+    """All-zero rows (masked voxels): after the first solve y == z everywhere, no weight is left, z stays 0."""
+    z, margin = als.als_reference(np.zeros((2, 7)), 1e5, 0.001, 10)
+    assert not z.any() and not margin.any()
 
 
 @pytest.mark.gpu

@@ -52,6 +52,8 @@ __global__ __launch_bounds__(256) void k_als_transpose_out(const double* __restr
 }
 
 // yt, zt, l1t, l2t, vt: [n][n_batch] doubles.  zt receives the baseline.
+// A spectrum with fewer than two non-zero weights (y == z at all points but one: an all-zero, masked voxel after its
+// first solve) has the singular matrix lam D'D, whose last pivots are 0: it has converged, and z keeps its value.
 __global__ __launch_bounds__(64) void k_als_solve(const double* __restrict__ yt, double* __restrict__ zt,
                                                   double* __restrict__ l1t, double* __restrict__ l2t,
                                                   double* __restrict__ vt, long long n_batch, int n, double lam,
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(64) void k_als_solve(const double* __restrict__ yt,
   for (int it = 0; it < n_iter; ++it) {
     // forward: factor A = L D L' (unit lower band L: l1 = L[i][i-1], l2 = L[i][i-2]) and solve L D v = W y
     double d1 = 1.0, d2 = 1.0, l1p = 0.0, u1 = 0.0, u2 = 0.0;
+    int n_weights = 0;
     for (int i = 0; i < n; ++i) {
       const long long o = (long long)i * nb + s;
       const double y = yt[o];
@@ -70,6 +73,7 @@ __global__ __launch_bounds__(64) void k_als_solve(const double* __restrict__ yt,
         const double z = zt[o];
         w = p * (double)(y > z) + (1.0 - p) * (double)(y < z);
       }
+      n_weights += w != 0.0;
       // D'D: diagonal 1,5,6,...,6,5,1; first off-diagonal -2,-4,...,-4,-2; second off-diagonal 1
       const double c0 = (i == 0 || i == n - 1) ? 1.0 : ((i == 1 || i == n - 2) ? 5.0 : 6.0);
       const double a_im1 = (i == 1 || i == n - 1) ? -2.0 * lam : -4.0 * lam;  // A[i][i-1]
@@ -87,6 +91,7 @@ __global__ __launch_bounds__(64) void k_als_solve(const double* __restrict__ yt,
       u2 = u1;
       u1 = u;
     }
+    if (n_weights < 2) break;  // singular: the sweep above wrote l1t, l2t and vt only
     // backward: L' z = v
     double z1 = 0.0, z2 = 0.0, l1n = 0.0, l2n = 0.0, l2nn = 0.0;  // l1[i+1], l2[i+1], l2[i+2]
     for (int i = n - 1; i >= 0; --i) {
