@@ -1,7 +1,7 @@
 """numpy restatement of the workgroup toolbox (xmris_amd/csrc/xm_wg.h), the oracle of tests/test_wg.py and
 tests/test_gpu_wg.py: the fixed tree of wg_sum, the two Gram maps, the round-robin pairing, a plain row-cyclic Jacobi in
-fp64, lmfit's transforms and a Cholesky solve in np.longdouble (80-bit, eps 1.08e-19), and the matrix families the GPU
-tests run.  tests/test_wg.py pins every piece before it judges a kernel."""
+fp64, lmfit's transforms and a Cholesky solve in np.longdouble (80-bit, eps 1.08e-19), the row-after-row sums of lm_normal
+(xm_lm.h), and the matrix families the GPU tests run.  tests/test_wg.py pins every piece before it judges a kernel."""
 import numpy as np
 
 EPS = np.finfo(np.float64).eps
@@ -274,6 +274,45 @@ def transform_scale(lo, hi, *vals):
 
 def lm_scale(d):
     return np.where(d > 0, d, 1.0)
+
+
+LM_STAGE_BYTES = 65536  # XM_LM_STAGE_BYTES
+# every branch of lm_normal (xm_lm.h): ne = (P + 1)(P + 2) / 2 - 1 entries over 256 threads, and the tiers of q_pts
+LM_NORMAL_P = (1,    # ne = 2: almost every lane idle
+               21,   # ne = 252: the last size with one entry per thread
+               22,   # ne = 275: the first with two
+               31,   # the highest P of the tier q_pts = 128
+               32,   # the lowest of q_pts = 64
+               63,   # the highest of q_pts = 64
+               64,   # the lowest of q_pts = 32
+               80)   # ne = 3320: all 13 entries per thread in use, the last one partly
+
+
+def lm_q_pts(p):
+    """Points per staging round of lm_normal at P = p: 128, 64 or 32 so that 2 q (p + 1) doubles fit the staging budget."""
+    q = 128
+    while q > 32 and 2 * q * (p + 1) * 8 > LM_STAGE_BYTES:
+        q //= 2
+    return q
+
+
+def lm_normal_cases(p, n_points, n=3, seed=0):
+    """[n, n_points, 2, p + 1] fp64, the staged rows [J | r] the probe's model copies: normal values, every column scaled
+    by its own power of ten over four decades, so that a swapped (i, j) or a dropped row changes every sum."""
+    rng = np.random.default_rng([seed, p, n_points])
+    scale = 10.0 ** rng.uniform(-2.0, 2.0, (n, 1, 1, p + 1))
+    return rng.standard_normal((n, n_points, 2, p + 1)) * scale
+
+
+def lm_normal(rows):
+    """rows [n_rows, p + 1] fp64, the staged rows of one problem in order -> the (p + 1) x (p + 1) matrix of lm_normal's
+    sums: every entry starts at 0 and takes a[r][i] * a[r][j] row after row, the product rounded before it is added.
+    Its upper triangle is what the kernel owns: [:p, :p] above the diagonal H, the diagonal hd, [:p, p] g."""
+    a = np.asarray(rows, dtype=np.float64)
+    acc = np.zeros((a.shape[1], a.shape[1]))
+    for r in a:
+        acc = acc + np.outer(r, r)
+    return acc
 
 
 CHOL_LAMS = (0.0, 1e-3, 1e3)

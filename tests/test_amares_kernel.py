@@ -29,7 +29,7 @@ TIE = 1e-9  # accept / reject margins below this are too close to call
 
 
 def tier(P):
-    """Points per staging round as am_q_pts (xm_amares.hip) states it: 2 q (P + 1) doubles within 64 KiB."""
+    """Points per staging round as lm_q_pts (xm_lm.h) states it: 2 q (P + 1) doubles within 64 KiB."""
     return 128 if P <= 31 else 64 if P <= 63 else 32
 
 

@@ -1,4 +1,4 @@
-"""The workgroup toolbox (xmris_amd/csrc/xm_wg.h) part by part on the GPU, through the probe library
+"""The workgroup toolbox (xmris_amd/csrc/xm_wg.h) and lm_normal (xm_lm.h) part by part on the GPU, through the probe library
 xmris_amd/libxmris_wgprobe.so (csrc/xm_wg_probe.hip), against tests/_wg_oracle.py.  The oracle's pieces, the matrix
 families and the bounds are pinned on the CPU in tests/test_wg.py; the bounds come from the reference side alone
 (tests/tool_wg_tolerance.py, profiles/wg_toolbox/tolerance.txt)."""
@@ -26,6 +26,7 @@ SIGNATURES = {  # the extern "C" entries of xm_wg_probe.hip, every one returning
     "xm_wgp_from_internal": [_p, _p, _p, _p, _p, _p, _l, _p],
     "xm_wgp_to_internal": [_p, _p, _p, _p, _p, _l, _p],
     "xm_wgp_ticket": [_p, _p, _p, _l, _i, _p],
+    "xm_wgp_lm_normal": [_p, _p, _p, _l, _i, _i, _p],
 }
 INVALID = -1  # XM_ERR_INVALID_ARG
 
@@ -99,6 +100,10 @@ def test_refusals_launch_nothing():
         ("xm_wgp_to_internal", (b, b, b, b, b, -1)), ("xm_wgp_to_internal", (None, b, b, b, b, 4)),
         ("xm_wgp_ticket", (b, b, b, -1, 4)), ("xm_wgp_ticket", (b, b, b, 4, 0)), ("xm_wgp_ticket", (b, b, b, 4, 1025)),
         ("xm_wgp_ticket", (None, b, b, 4, 4)),
+        ("xm_wgp_lm_normal", (b, b, b, 1, 1, 0)), ("xm_wgp_lm_normal", (b, b, b, 1, 1, 81)), ("xm_wgp_lm_normal", (b, b, b, 1, 0, 4)),
+        ("xm_wgp_lm_normal", (b, b, b, 1, -1, 4)), ("xm_wgp_lm_normal", (b, b, b, -1, 1, 4)),
+        ("xm_wgp_lm_normal", (b, b, b, (1 << 20) + 1, 1, 4)), ("xm_wgp_lm_normal", (None, b, b, 1, 1, 4)),
+        ("xm_wgp_lm_normal", (b, None, b, 1, 1, 4)), ("xm_wgp_lm_normal", (b, b, None, 1, 1, 4)),
     ]
     for name, args in bad:
         assert getattr(lib, name)(*args, None) == INVALID, (name, args)
@@ -298,6 +303,27 @@ def test_cholesky_and_solve_at_every_size(lo):
     print(f"cholesky P={lo}..{lo + 19}: L L^T {worst['factor']:.2f} units of eps ||H + lam D||_F, "
           f"{worst['factor'] / CHOL_TOL['factor']:.3f} of its bound; dl {worst['solution']:.2e} units of eps cond max |x|, "
           f"{worst['solution'] / CHOL_TOL['solution']:.3f} of its bound; largest cond {worst['cond']:.1e}")
+
+
+# ---- lm_normal (xm_lm.h) ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", orc.LM_NORMAL_P)
+def test_lm_normal_is_the_row_after_row_sum_bit_for_bit(p):
+    """The probes are built without contraction: every product is rounded, then added, as the oracle does."""
+    q = orc.lm_q_pts(p)
+    upper, diag = np.triu(np.ones((p, p), bool), 1), np.eye(p, dtype=bool)
+    for n_points in (1, q, q + 1):  # one ragged round; one full round; a full round, then a ragged one
+        cases = orc.lm_normal_cases(p, n_points)
+        n = len(cases)
+        h_out, vec_out = _out((n, p, p), np.float64), _out((n, 7, p), np.float64)
+        _call("xm_wgp_lm_normal", _up(cases), h_out, vec_out, n, n_points, p)
+        h, vec = h_out.cpu().numpy(), vec_out.cpu().numpy()
+        for k in range(n):
+            want = orc.lm_normal(cases[k].reshape(2 * n_points, p + 1))
+            assert np.array_equal(_bits(h[k][upper]), _bits(want[:p, :p][upper])), (p, n_points, k, "H")
+            assert np.array_equal(_bits(vec[k, 0]), _bits(want[:p, :p][diag])), (p, n_points, k, "hd")
+            assert np.array_equal(_bits(vec[k, 2]), _bits(want[:p, p])), (p, n_points, k, "g")
+        # nothing else is written: H on and below the diagonal, and dsc, u, ut, dl, ld
+        assert np.all(h[:, ~upper] == -7.0) and np.all(vec[:, [1, 3, 4, 5, 6]] == -7.0), (p, n_points)
 
 
 # ---- wg_from_internal, wg_to_internal -------------------------------------------------------------------------------------

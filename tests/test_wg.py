@@ -205,6 +205,41 @@ def test_longdouble_cholesky_solves():
         assert orc.cholesky_quality(m, g[k], low.astype(float) * (1 + 1e-9), x.astype(float))[0] > 1e3
 
 
+# ---- normal equations -------------------------------------------------------------------------------------------------------
+def test_lm_q_pts_tiers_are_the_staging_budget():
+    for p in range(1, orc.MAXP + 1):
+        q = orc.lm_q_pts(p)
+        assert q in (128, 64, 32) and (q == 32 or 2 * q * (p + 1) * 8 <= orc.LM_STAGE_BYTES)
+        assert q == 128 or 2 * (2 * q) * (p + 1) * 8 > orc.LM_STAGE_BYTES  # the largest tier that fits
+    assert [orc.lm_q_pts(p) for p in orc.LM_NORMAL_P] == [128, 128, 128, 128, 64, 64, 32, 32]
+    ne = [(p + 1) * (p + 2) // 2 - 1 for p in orc.LM_NORMAL_P]
+    assert [-(-e // orc.NT) for e in ne] == [1, 1, 2, 3, 3, 9, 9, 13] and ne[1] == 252 and ne[2] == 275 and ne[-1] == 3320
+
+
+@pytest.mark.parametrize("p", orc.LM_NORMAL_P)
+def test_lm_normal_oracle_is_the_product_of_the_staged_rows(p):
+    """Against A^T A of the staged rows A = [J | r].  Both are sums of the same n products in some order: each is within
+    gamma_n sum |a_ri a_rj| of the exact sum (gamma_n < n eps), so they differ by at most 2 n eps (|A|^T |A|)_ij."""
+    q = orc.lm_q_pts(p)
+    for n_points in (1, q, q + 1):
+        cases = orc.lm_normal_cases(p, n_points)
+        assert cases.shape == (3, n_points, 2, p + 1)
+        decades = np.log10(np.abs(cases).max(axis=(1, 2)))
+        assert p < 8 or np.all(decades.max(axis=1) - decades.min(axis=1) > 2)  # the columns span decades
+        for case in cases:
+            a = case.reshape(2 * n_points, p + 1)
+            got = orc.lm_normal(a)
+            assert np.array_equal(got, got.T)
+            bound = 2 * len(a) * orc.EPS * (np.abs(a).T @ np.abs(a))
+            assert np.all(np.abs(got - a.T @ a) <= bound)
+            if n_points > 1:  # a dropped row or a transposed pair of columns is far outside the bound
+                assert np.all(np.abs(orc.lm_normal(a[1:]) - a.T @ a) > bound)
+    one = orc.lm_normal(np.array([[3.0, 0.1, 7.0]]))  # one row: the rounded products themselves
+    assert np.array_equal(one, np.outer([3.0, 0.1, 7.0], [3.0, 0.1, 7.0]))
+    two = orc.lm_normal(np.array([[1e16, 1.0], [1.0, 1.0], [-1e16, 1.0]]))  # row after row: (1e16 + 1) - 1e16 = 0
+    assert two[0, 1] == 0.0 and two[1, 1] == 3.0
+
+
 # ---- transforms -------------------------------------------------------------------------------------------------------------
 def test_transforms_are_lmfits_and_invert_each_other():
     bt, u, lo, hi, v = orc.transform_grid()

@@ -9,16 +9,6 @@ static int am_fail(const std::string& msg) { return xm_fail(XM_ERR_INVALID_ARG, 
 
 namespace {
 XmResidency g_am_res, g_am_res_linked;  // one residency record per kernel instantiation
-
-int am_q_pts(int lda) {  // points per staging round: 128, 64 or 32 so that 2 q lda doubles fit the staging budget
-  int q = 128;
-  while (q > 32 && 2 * (size_t)q * lda * sizeof(double) > XM_AM_STAGE_BYTES) q >>= 1;
-  return q;
-}
-
-size_t am_lds_bytes(int P, int lda, int q) {
-  return ((size_t)P * P + 7 * (size_t)P + 2 * XM_AM_MAXQ + XM_AM_NT + 2 * (size_t)q * lda) * sizeof(double);
-}
 }  // namespace
 
 extern "C" {
@@ -119,20 +109,8 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
       continue;
     }
     A.col[q] = (signed char)P++;
-    const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
-    if (fl && fh) {
-      A.bt[q] = XM_WG_TWO;
-      A.u0[q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
-    } else if (fl) {
-      A.bt[q] = XM_WG_LO;
-      A.u0[q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
-    } else if (fh) {
-      A.bt[q] = XM_WG_HI;
-      A.u0[q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
-    } else {
-      A.bt[q] = XM_WG_FREE;
-      A.u0[q] = v;
-    }
+    A.bt[q] = lm_bound_type(lo, hi);
+    A.u0[q] = lm_start_value(A.bt[q], v, lo, hi);
   }
   // A linked parameter: the root's column, transform and bounds; its own `lower` / `upper` / `init` / `fixed` are not
   // read.  A follower of a fixed root is fixed at the mapped value.
@@ -161,7 +139,7 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
 
   A.P = P;
   A.lda = P + 1;
-  A.q_pts = am_q_pts(A.lda);
+  A.q_pts = lm_q_pts(A.lda);
   A.params = params;
   A.asd = amp_sd;
   A.rss = rss;
@@ -172,10 +150,10 @@ int xm_amares_fit_linked(const void* in, int64_t in_row_stride, int64_t n_batch,
 
   DeviceGuard guard(in);
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = am_lds_bytes(P, A.lda, A.q_pts);
+  const size_t lds = lm_lds_bytes(P, A.lda, A.q_pts, XM_AM_MAXQ);
   if (any_link)  // <LINKED, free columns>
-    return xm_launch_items(g_am_res_linked, k_amares_fit<true>, XM_AM_NT, lds, n_batch, A, st, "k_amares_fit", "true", P, -1);
-  return xm_launch_items(g_am_res, k_amares_fit<false>, XM_AM_NT, lds, n_batch, A, st, "k_amares_fit", "false", P, -1);
+    return xm_launch_items(g_am_res_linked, k_amares_fit<true>, XM_WG_NT, lds, n_batch, A, st, "k_amares_fit", "true", P, -1);
+  return xm_launch_items(g_am_res, k_amares_fit<false>, XM_WG_NT, lds, n_batch, A, st, "k_amares_fit", "false", P, -1);
 }
 
 }  // extern "C"

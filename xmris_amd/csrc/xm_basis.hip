@@ -10,16 +10,6 @@ static int bs_fail(const std::string& msg) { return xm_fail(XM_ERR_INVALID_ARG, 
 namespace {
 XmResidency g_bs_res;
 
-int bs_q_pts(int lda) {  // points per staging round: 128, 64 or 32 so that 2 q lda doubles fit the staging budget
-  int q = 128;
-  while (q > 32 && 2 * (size_t)q * lda * sizeof(double) > XM_BS_STAGE_BYTES) q >>= 1;
-  return q;
-}
-
-size_t bs_lds_bytes(int P, int lda, int q) {
-  return ((size_t)P * P + 7 * (size_t)P + 2 * XM_BS_MAXQ + XM_BS_NT + 2 * (size_t)q * lda) * sizeof(double);
-}
-
 // ord / gs: the metabolites sorted by group (ascending m within a group).  Nonzero: an index out of range or an empty group
 template <class Args>
 int bs_groups(Args& A, const int32_t* group, int M, int G) {
@@ -119,21 +109,13 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
     }
     if (P >= XM_BS_MAXP) return bs_fail("more than " + std::to_string(XM_BS_MAXP) + " free parameters");
     A.col[q] = (signed char)P++;
-    const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
-    A.bt[q] = fl && fh ? XM_WG_TWO : fl ? XM_WG_LO : fh ? XM_WG_HI : XM_WG_FREE;
+    A.bt[q] = lm_bound_type(lo, hi);
     if (automatic) {
       A.u0[q] = NAN;  // the kernel starts it per voxel
       continue;
     }
     const double v = std::fmin(std::fmax(init[q], lo), hi);  // initial values are clipped into their bounds
-    if (A.bt[q] == XM_WG_TWO)
-      A.u0[q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
-    else if (A.bt[q] == XM_WG_LO)
-      A.u0[q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
-    else if (A.bt[q] == XM_WG_HI)
-      A.u0[q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
-    else
-      A.u0[q] = v;
+    A.u0[q] = lm_start_value(A.bt[q], v, lo, hi);
   }
   if (P < 1) return bs_fail("every parameter is fixed");
   if (n - skip < P)
@@ -155,7 +137,7 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
   A.P = P;
   A.max_iter = max_iter;
   A.lda = P + 1;
-  A.q_pts = bs_q_pts(A.lda);
+  A.q_pts = lm_q_pts(A.lda);
   A.ftol = ftol;
   A.xtol = xtol;
   A.params = params;
@@ -168,11 +150,11 @@ int xm_basis_fit(const void* in, int64_t in_row_stride, int64_t n_batch, int n, 
 
   DeviceGuard guard(in);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_basis_norms, dim3((unsigned)M), dim3(XM_BS_NT), 0, st, A.basis, n, skip,
+  hipLaunchKernelGGL(k_basis_norms, dim3((unsigned)M), dim3(XM_WG_NT), 0, st, A.basis, n, skip,
                      (double*)((char*)workspace + 256));
   HIP_TRY(hipGetLastError());
-  return xm_launch_items(g_bs_res, k_basis_fit, XM_BS_NT, bs_lds_bytes(P, A.lda, A.q_pts), n_batch, A, st, "k_basis_fit",
-                         "fma", P, M);  // <J^T J form, free columns, metabolites>
+  return xm_launch_items(g_bs_res, k_basis_fit, XM_WG_NT, lm_lds_bytes(P, A.lda, A.q_pts, XM_BS_MAXQ), n_batch, A, st,
+                         "k_basis_fit", "fma", P, M);  // <J^T J form, free columns, metabolites>
 }
 
 }  // extern "C"

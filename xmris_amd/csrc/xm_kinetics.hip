@@ -1,6 +1,7 @@
 // Host side of xm_kinetics_fit (include/xmris_hip.h); the kernel is in xm_kinetics.h.
 #include "xm_host.h"
 #include "xm_kinetics.h"
+#include "xm_lm.h"  // lm_bound_type, lm_start_value: the host-side start transform is all the kernel shares with it
 
 #include <cmath>
 #include <string>
@@ -67,21 +68,13 @@ extern "C" int xm_kinetics_fit(const double* substrate, const double* products, 
         continue;
       }
       A.col[m][q] = P++;
-      const bool fl = std::isfinite(lo), fh = std::isfinite(hi);
-      A.bt[m][q] = fl && fh ? XM_WG_TWO : fl ? XM_WG_LO : fh ? XM_WG_HI : XM_WG_FREE;
+      A.bt[m][q] = lm_bound_type(lo, hi);
       if (automatic) {
         A.u0[m][q] = NAN;  // the kernel starts it per item
         continue;
       }
       const double v = std::fmin(std::fmax(v0, lo), hi);  // initial values are clipped into their bounds
-      if (A.bt[m][q] == XM_WG_TWO)
-        A.u0[m][q] = std::asin(std::fmin(std::fmax(2.0 * (v - lo) / (hi - lo) - 1.0, -1.0), 1.0));
-      else if (A.bt[m][q] == XM_WG_LO)
-        A.u0[m][q] = std::sqrt((v - lo + 1.0) * (v - lo + 1.0) - 1.0);
-      else if (A.bt[m][q] == XM_WG_HI)
-        A.u0[m][q] = std::sqrt((hi - v + 1.0) * (hi - v + 1.0) - 1.0);
-      else
-        A.u0[m][q] = v;
+      A.u0[m][q] = lm_start_value(A.bt[m][q], v, lo, hi);
     }
     if (P < 1) return kin_fail("product " + std::to_string(m) + ": every parameter is fixed");
     A.n_free[m] = P;

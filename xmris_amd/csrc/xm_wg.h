@@ -286,6 +286,8 @@ XM_DEV int wg_jacobi(double* G, double* V, double* red, double* rot, int C) {
 }
 
 // ---- Levenberg-Marquardt leaves (real P x P normal equations, row-major) ---------------------------------------------
+// Used by the driver of k_amares_fit and k_basis_fit (xm_lm.h: the normal equations, the LM loop and the CRLB pass are
+// there, once); k_kinetics_fit, one wave per item, uses the transforms, the bound types and the Marquardt scale alone.
 
 // bound types (lmfit's transforms)
 enum { XM_WG_FIXED = 0, XM_WG_FREE = 1, XM_WG_LO = 2, XM_WG_HI = 3, XM_WG_TWO = 4 };

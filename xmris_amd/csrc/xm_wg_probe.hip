@@ -1,14 +1,16 @@
-// libxmris_wgprobe.so -- test-only probes of the workgroup toolbox (xm_wg.h), outside the product library: it is not
+// libxmris_wgprobe.so -- test-only probes of the workgroup toolbox (xm_wg.h) and of the normal-equation accumulation of
+// the Levenberg-Marquardt driver built on it (xm_lm.h), outside the product library: it is not
 // linked into libxmris_hip.so and not declared in include/xmris_hip.h.  Each kernel is one 256-thread workgroup per
 // problem: it stages its input in the LDS, calls one toolbox function and copies everything out, so that
 // tests/test_gpu_wg.py can hold every part to tests/_wg_oracle.py on its own.  The host side checks its arguments --
-// nothing else stands between a test and an LDS overrun -- and returns XM_ERR_INVALID_ARG without a launch.  The Gram
-// accumulation loops are not restated here: they stay in the users and are tested through them.
+// nothing else stands between a test and an LDS overrun -- and returns XM_ERR_INVALID_ARG without a launch.  The complex
+// Gram accumulation loops (wg_gram_*) are not restated here: they stay in the users and are tested through them.  The
+// real one of the fitting kernels is lm_normal itself, probed below with a model that copies given rows.
 #include "../../include/xmris_hip.h"
-#include "xm_wg.h"
+#include "xm_lm.h"
 
 #define XM_WGP_MAXC 64       // coils, patch voxels, Hankel rows: the largest Hermitian matrix of any user
-#define XM_WGP_MAXP 80       // XM_BS_MAXP, and AMARES's 5 x 16
+#define XM_WGP_MAXP XM_LM_MAXP  // XM_BS_MAXP, and AMARES's 5 x 16
 #define XM_WGP_MAXN (1 << 20)  // problems per launch
 
 static_assert(XM_WG_NT == 256, "the probes lay their outputs out per 256 threads");
@@ -126,6 +128,39 @@ __global__ __launch_bounds__(XM_WG_NT) void k_wgp_to_internal(const int* bt, con
   if (i < n) u[i] = wg_to_internal(bt[i], v[i], lo[i], hi[i]);
 }
 
+// lm_normal with a model whose staged rows are given: in [n][n_points][2][P + 1] -> h_out [n][P][P], vec_out [n][7][P]
+// (hd, dsc, g, u, ut, dl, ld), all of it -7 before lm_normal: it writes the strict upper triangle of H, hd and g only
+struct WgpLmArgs {
+  const double* in;
+  double *h_out, *vec_out;
+  int n, P, lda, q_pts;
+};
+
+struct WgpLmModel {
+  using Args = WgpLmArgs;
+  XM_DEV static int first(const Args&) { return 0; }
+  XM_DEV static int count(const Args& A) { return A.n; }
+  XM_DEV static void stage_point(const Args& A, const LmLds&, long long row, int i, bool, double* r0, double* r1) {
+    const double* src = A.in + ((size_t)row * A.n + i) * 2 * (A.P + 1);
+    for (int c = 0; c <= A.P; ++c) {
+      r0[c] = src[c];
+      r1[c] = src[A.P + 1 + c];
+    }
+  }
+};
+
+__global__ __launch_bounds__(XM_WG_NT) void k_wgp_lm_normal(WgpLmArgs A) {
+  extern __shared__ double lds[];
+  const int t = threadIdx.x, P = A.P, nh = P * P + 7 * P;  // H and the seven vectors are contiguous from L.H
+  const LmLds L = lm_carve(lds, P, 0);
+  for (int e = t; e < nh; e += XM_WG_NT) L.H[e] = -7.0;
+  __syncthreads();
+  lm_normal<WgpLmModel>(A, L, blockIdx.x, false);
+  const size_t b = blockIdx.x;
+  for (int e = t; e < P * P; e += XM_WG_NT) A.h_out[b * P * P + e] = L.H[e];
+  for (int e = t; e < 7 * P; e += XM_WG_NT) A.vec_out[b * 7 * P + e] = L.hd[e];
+}
+
 // the loop of every user: who[item] = the workgroup that drew it, drawn[item] += 1
 __global__ __launch_bounds__(XM_WG_NT) void k_wgp_ticket(unsigned* counter, int* who, int* drawn, long long n_items) {
   __shared__ unsigned next;
@@ -224,6 +259,16 @@ int xm_wgp_to_internal(const int* bt, const double* v, const double* lo, const d
   if (n == 0) return XM_OK;
   hipLaunchKernelGGL(k_wgp_to_internal, dim3((unsigned)((n + XM_WG_NT - 1) / XM_WG_NT)), dim3(XM_WG_NT), 0,
                      (hipStream_t)stream, bt, v, lo, hi, u, n);
+  return launched();
+}
+
+int xm_wgp_lm_normal(const double* in, double* h_out, double* vec_out, long long n, int n_points, int P, void* stream) {
+  if (!in || !h_out || !vec_out || !count_ok(n) || n_points < 1 || P < 1 || P > XM_WGP_MAXP) return XM_ERR_INVALID_ARG;
+  if (n == 0) return XM_OK;
+  WgpLmArgs A{in, h_out, vec_out, n_points, P, P + 1, lm_q_pts(P + 1)};
+  const size_t lds = lm_lds_bytes(P, A.lda, A.q_pts, 0);  // about 100 KiB at P = 63
+  if (const int rc = opt_in(k_wgp_lm_normal, lds)) return rc;
+  hipLaunchKernelGGL(k_wgp_lm_normal, dim3((unsigned)n), dim3(XM_WG_NT), lds, (hipStream_t)stream, A);
   return launched();
 }
 
