@@ -272,10 +272,11 @@ def make_basis(M, n, dt, seed):
 
 
 def kernel_case(M, G, n, seed, lineshape="voigt", fit_phase=True, skip=0, n_vox=2, dt=2.5e-4, noise=0.02,
-                amplitude_start=None, absent=()):
+                amplitude_start=None, absent=(), fixed_amplitudes=0):
     """Seeded case: basis, group = m mod G (so that the groups interleave), per-case truth inside the bounds (shift
     +-4 Hz, Lorentzian 1 ... 5 Hz, Gaussian 1 ... 5 Hz for voigt, phase +-0.4 rad, amplitudes 0.5 ... 2; the
-    metabolites in `absent` have amplitude 0) and n_vox voxels that differ in their noise.  Returns a dict: x
+    metabolites in `absent` have amplitude 0; the first `fixed_amplitudes` of the metabolites 0, 3, 6, ... are fixed at 0.9
+    of their true amplitude) and n_vox voxels that differ in their noise.  Returns a dict: x
     [n_vox, n] complex128, B, group, dt, skip, truth [Q], init, lo, hi, fixed [Q], M, G."""
     rng = np.random.default_rng([seed, M, G, n])
     B = make_basis(M, n, dt, seed)
@@ -290,6 +291,9 @@ def kernel_case(M, G, n, seed, lineshape="voigt", fit_phase=True, skip=0, n_vox=
     if lineshape == "voigt":
         truth[M + 2 * G:M + 3 * G] = gaussian_damping(rng.uniform(1.0, 5.0, G))
     truth[-1] = rng.uniform(-0.4, 0.4) if fit_phase else 0.0
+    held = np.arange(0, M, 3)[:fixed_amplitudes]
+    assert held.size == fixed_amplitudes
+    init[held], fixed[held] = 0.9 * truth[held], True
     z = rng.standard_normal((n_vox, n)) + 1j * rng.standard_normal((n_vox, n))
     x = model(truth, B, group, dt)[None] + noise * z
     return {"x": x, "B": B, "group": group, "dt": dt, "skip": skip, "truth": truth, "init": init, "lo": lo, "hi": hi,

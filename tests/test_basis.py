@@ -351,3 +351,29 @@ def test_scipy_converges_on_the_parity_cases(name):
         assert o["success"] and o["status"] in (1, 2, 3, 4), (v, o["status"])
         assert np.all(np.isfinite(o["sd"])) and np.all(o["sd"][:c["M"]] > 0)
         assert np.all(o["params"][:c["M"]] > 0)  # no amplitude ends on its bound: the standard deviations mean something
+
+
+def test_shapes_of_the_second_crlb_round_are_conditioned():
+    """M70G3 and M100G2 with 30 fixed amplitudes (tests/test_gpu_basis.py: more amplitudes than one round of the CRLB pass
+    hands out) at the truth, over every variant and every n of N_LIST: 64 eps cond(J^T J) < 1, so _check_invariants
+    compares every deviation of these shapes, those of the second round included, and does not skip."""
+    import test_gpu_basis as g
+
+    eps = np.finfo(np.float64).eps
+    for shape, span in (("M70G3", (1e-11, 2.7e-2)), ("M100G2", (1e-12, 1.2e-3))):
+        M, G = g.SHAPES[shape]
+        held = g.FIXED_AMPLITUDES.get(shape, 0)
+        seen = []
+        for vi, (lineshape, fit_phase, skip, _) in enumerate(g.VARIANTS):
+            P = M - held + (3 if lineshape == "voigt" else 2) * G + int(fit_phase)
+            assert 65 <= P <= 80 and M > 2 * 32 * (P + 1) // P  # q_pts = 32: a second round
+            for n in g.N_LIST:
+                nn = P + skip if n == "P" else n
+                c = orc.kernel_case(M, G, nn, 100 + vi, lineshape=lineshape, fit_phase=fit_phase, skip=skip, n_vox=2,
+                                    fixed_amplitudes=held)
+                free = ~(c["fixed"] | (c["lo"] == c["hi"]))
+                assert np.count_nonzero(free) == P and np.count_nonzero(~free[:M]) == held
+                sd, cond = orc.amplitude_sd(c["B"], c["group"], c["dt"], c["truth"], c["lo"], c["hi"], c["fixed"], skip)
+                assert np.all(sd[free[:M]] > 0) and np.all(sd[~free[:M]] == 0)
+                seen.append(64 * eps * cond)
+        assert span[0] <= min(seen) and max(seen) <= span[1], (shape, min(seen), max(seen))

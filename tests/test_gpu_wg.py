@@ -15,7 +15,7 @@ from test_wg import CHOL_TOL, JACOBI_TOL, OFF_TOL, TRANSFORM_TOL
 pytestmark = pytest.mark.gpu
 
 EPS = orc.EPS
-_p, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+_p, _i, _l, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double
 SIGNATURES = {  # the extern "C" entries of xm_wg_probe.hip, every one returning an int status
     "xm_wgp_sum": [_p, _p, _l, _p],
     "xm_wgp_mirror": [_p, _p, _l, _i, _p],
@@ -27,6 +27,7 @@ SIGNATURES = {  # the extern "C" entries of xm_wg_probe.hip, every one returning
     "xm_wgp_to_internal": [_p, _p, _p, _p, _p, _l, _p],
     "xm_wgp_ticket": [_p, _p, _p, _l, _i, _p],
     "xm_wgp_lm_normal": [_p, _p, _p, _l, _i, _i, _p],
+    "xm_wgp_lm_fit": [_i, _p, _p, _l, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _d, _d] + [_p] * 8 + [_i, _p],  # tests/test_gpu_lm.py
 }
 INVALID = -1  # XM_ERR_INVALID_ARG
 
